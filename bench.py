@@ -7,15 +7,25 @@ engine: strategy generation (constrained JSON), 6 branch rollouts of 5
 user+assistant turns each (sequential per branch, batched across
 branches), one comparative forced-ranking judge pass, prune + backprop.
 Every step uses fresh synthetic prompts (step-salted) so nothing is served
-from a previous step's KV.
+from a previous step's KV. The bench steps the serving engine from the
+search's event loop whenever all search coroutines wait on it
+(drive_lockstep), which makes the batches, and so the outputs, repeat
+exactly from run to run at the same throughput as the engine thread.
 
 Weak scaling: with --gpus N the ONE search has init_branches = 6*N,
 branches sharded round-robin across ranks (SPMD DP — dts_amd/search/
 dist_engine.py); per-GPU work stays 6 branches. value = scored
 trajectories per second aggregated over the whole job.
 
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps search rounds, optionally write the last step's outputs
+(--dump-outputs DIR) and print one JSON result line. --full is the switch
+for any extended measurement that needs runs of its own; there is none at
+present (the engine counters and per-phase wall clock in the result line
+are by-products of the timed steps), so it only marks the result line.
+
 Launch (driver contract):
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 """
@@ -54,7 +64,27 @@ def parse_args():
                         "user_variability=True, K intents per branch)")
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--kv-frac", type=float, default=0.75)
-    return p.parse_args()
+    p.add_argument(
+        "--dump-outputs",
+        type=str,
+        default=None,
+        metavar="DIR",
+        help="after the timed steps write what the LAST timed search "
+        "returned (scores, prune flags, dialogue bytes) as DIR/<name>.npy",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the extended measurements that need runs of their "
+        "own (none at present: a plain run already reports everything "
+        "from the timed steps)",
+    )
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
 
 
 GOAL = (
@@ -95,15 +125,116 @@ def build_config(args, world, seed):
     )
 
 
-async def run_search(llm, cfg, dp, rounds=1):
+async def drive_lockstep(search, engines):
+    """Step the serving engines from the search's own event loop, and only
+    while every search coroutine is parked on an engine future.
+
+    With the engines on their own threads, which requests share a batch
+    depends on how the two threads interleave; batch size picks the GEMM
+    kernel, so bf16 logits, sampled tokens and finally scores drifted from
+    run to run. Here a batch is scheduled only once all requests that the
+    delivered results give rise to have been submitted, so the sequence of
+    batches, and with it every output, is a function of the arguments."""
+    loop = asyncio.get_running_loop()
+    ready = loop._ready  # callbacks due in the next loop iteration
+    while not search.done():
+        await asyncio.sleep(0)
+        if ready:
+            continue  # some coroutine can still run: requests may follow
+        ran = False
+        for e in engines:
+            ran = e.step() or ran
+        if not ran:
+            await asyncio.sleep(0.001)  # only timers pending (retry backoff)
+
+
+async def run_search(llm, cfg, dp, engines, rounds=1):
     from dts_amd.search.dist_engine import DistributedDTSEngine
 
     engine = DistributedDTSEngine(llm, cfg, dp=dp)
-    result = await engine.run(rounds=rounds)
+    search = asyncio.ensure_future(engine.run(rounds=rounds))
+    await drive_lockstep(search, engines)
+    result = search.result()
     scored = sum(
         1 for n in result.all_nodes if n.strategy is not None and n.stats.judge_scores
     )
-    return scored, engine.phase_times
+    return scored, engine.phase_times, result
+
+
+# --dump-outputs budget: the dialogue text is the only array that grows
+# with the search size; rows past this many bytes are dropped whole
+# (deterministically, in tree order) so the directory stays far below 64 MB.
+_DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(result, out_dir):
+    """Write what a caller of the timed search receives (DTSRunResult) as
+    float64/float32 .npy arrays, one row per strategy branch in tree order
+    (node ids are random, the order is not):
+
+      aggregated_score.npy [B]     f64  median judge score of the branch
+      judge_scores.npy     [B, J]  f64  individual judge scores, -1 padded
+      value_mean.npy       [B]     f64  backpropagated value
+      visits.npy           [B]     f64
+      pruned.npy           [B]     f32  1 where the branch was pruned
+      best.npy             [2]     f64  (row index of the best leaf, score)
+      message_bytes.npy    [B, L]  f32  UTF-8 bytes of the branch's dialogue
+                                        (messages joined by 0x1e), -1 padded
+      message_lengths.npy  [B, M]  f32  bytes per message, -1 padded
+
+    The inputs (prompts, weights, sampling seeds) are a function of the
+    arguments alone, and drive_lockstep makes the batching one too, so two
+    runs with the same arguments write identical files (checked bit for
+    bit on CPU fp32 and on one MI355X in bf16)."""
+    import numpy as np
+
+    from dts_amd.search.types import NodeStatus
+
+    os.makedirs(out_dir, exist_ok=True)
+    nodes = [n for n in result.all_nodes if n.strategy is not None]
+    B = len(nodes)
+
+    def padded(rows, dtype):
+        width = max((len(r) for r in rows), default=0)
+        arr = np.full((len(rows), width), -1, dtype=dtype)
+        for i, r in enumerate(rows):
+            arr[i, : len(r)] = r
+        return arr
+
+    texts = [
+        [(m.content or "").encode("utf-8") for m in n.messages] for n in nodes
+    ]
+    rows, budget = [], _DUMP_MAX_BYTES // 4
+    for msgs in texts:
+        row = list(b"\x1e".join(msgs))
+        width = max([len(row)] + [len(r) for r in rows])
+        if width * (len(rows) + 1) > budget:
+            break
+        rows.append(row)
+    best_row = next(
+        (i for i, n in enumerate(nodes) if n.id == result.best_node_id), -1
+    )
+    arrays = {
+        "aggregated_score": np.array(
+            [n.stats.aggregated_score for n in nodes], dtype=np.float64
+        ),
+        "judge_scores": padded(
+            [[float(x) for x in n.stats.judge_scores] for n in nodes], np.float64
+        ),
+        "value_mean": np.array([n.stats.value_mean for n in nodes], dtype=np.float64),
+        "visits": np.array([n.stats.visits for n in nodes], dtype=np.float64),
+        "pruned": np.array(
+            [n.status == NodeStatus.PRUNED for n in nodes], dtype=np.float32
+        ),
+        "best": np.array([best_row, result.best_score], dtype=np.float64),
+        "message_bytes": padded(rows, np.float32),
+        "message_lengths": padded(
+            [[len(m) for m in msgs] for msgs in texts], np.float32
+        ),
+    }
+    assert B == 0 or sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def main():
@@ -161,6 +292,8 @@ def main():
             weight_seed=1,
         )
     backend = LocalBackend(engines, default_model=args.model)
+    # the bench steps the engines itself (drive_lockstep), not their threads
+    backend.shutdown()
     llm = LLM(backend, default_model=args.model)
 
     def sync():
@@ -174,13 +307,17 @@ def main():
         cfg = type(cfg)(**{**cfg.__dict__,
                            "goal": f"{GOAL} (scenario {step_idx})",
                            "first_message": f"{FIRST_MESSAGE} (case {step_idx})"})
-        scored, phases = asyncio.run(run_search(llm, cfg, dp, rounds=args.rounds))
+        scored, phases, result = asyncio.run(
+            run_search(llm, cfg, dp, list(engines.values()), rounds=args.rounds)
+        )
         for k, v in phases.items():
             phase_totals[k] = phase_totals.get(k, 0.0) + v
+        last_result[0] = result
         return scored
 
     # warmup
     phase_totals: dict = {}
+    last_result: list = [None]
     for w in range(args.warmup):
         one_step(10_000 + w)
 
@@ -208,6 +345,9 @@ def main():
     traj_per_sec = total_scored / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last_result[0], args.dump_outputs)
+
     if rank == 0:
         stats = engine.cache_stats
         print(
@@ -219,6 +359,7 @@ def main():
                     "n_gpus": n_gpus,
                     "steps": args.steps,
                     "warmup": args.warmup,
+                    "full": args.full,
                     "ms_per_step": round(ms_per_step, 1),
                     "higher_is_better": True,
                     "scaling": "weak",
