@@ -118,9 +118,11 @@ class LlamaMLP(nn.Module):
         self.inter_per_rank = spec.intermediate_size // tp.size
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        gu = self.gate_up_proj(x)
-        # column-parallel layout: [gate_shard | up_shard] per rank
-        return self.down_proj(ops.silu_mul(gu))
+        # column-parallel layout: [gate_shard | up_shard] per rank, no
+        # gather, so the per-rank weight is itself a [2*I_rank, K] gate_up
+        gup = self.gate_up_proj
+        assert gup.bias is None and not gup.gather_output
+        return self.down_proj(ops.linear_swiglu(x, gup.weight))
 
 
 class LlamaLayer(nn.Module):

@@ -31,7 +31,10 @@ void top_p_sample_v2(torch::Tensor out, torch::Tensor logits,
                      torch::Tensor ws_bins, torch::Tensor ws_slice,
                      torch::Tensor ws_tau);
 void gemv_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w);
-void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w);
+void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                      int64_t tiles_per_wg, int64_t unroll);
+void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
+                             torch::Tensor w);
 void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                         torch::Tensor counts, torch::Tensor offsets);
 
@@ -60,7 +63,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_bf16", &gemv_bf16,
         "skinny-batch (M<=8) bf16 weight-streaming GEMV");
   m.def("gemm_skinny_bf16", &gemm_skinny_bf16,
-        "skinny-M (M<=16) bf16 MFMA weight-streaming GEMM");
+        "skinny-M (M<=16) bf16 MFMA weight-streaming GEMM; tiles_per_wg "
+        "pins the N-tiles per workgroup (1/2/4), unroll the k-chunks in "
+        "flight (4/8; 8 needs K % 1024 == 0); 0 = auto",
+        py::arg("out"), py::arg("x"), py::arg("w"),
+        py::arg("tiles_per_wg") = 0, py::arg("unroll") = 0);
+  m.def("gemm_skinny_swiglu_bf16", &gemm_skinny_swiglu_bf16,
+        "skinny-M gate_up GEMM with fused SwiGLU epilogue: "
+        "out[M,I] = silu(x Wg^T) * (x Wu^T), w = [Wg; Wu]");
   m.def("moe_grouped_linear", &moe_grouped_linear,
         "grouped per-expert skinny GEMM (capture-safe MoE decode)");
 }

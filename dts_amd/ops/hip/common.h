@@ -28,6 +28,16 @@ DEV short f2bf(float f) {
   return (short)(c.i >> 16);
 }
 
+// SwiGLU on bf16 operands: silu(gate) * up, fp32 math, one bf16 rounding.
+// The ONE definition shared by silu_mul_kernel and the skinny GEMM's fused
+// epilogue, so the two paths cannot drift apart (they must agree bit for
+// bit: the engine's sampled tokens depend on it).
+DEV short swiglu_bf16(short gate, short up) {
+  float gf = bf2f(gate);
+  float s = gf / (1.f + __expf(-gf));
+  return f2bf(s * bf2f(up));
+}
+
 // wave-wide sum over 64 lanes
 DEV float wave_sum(float v) {
 #pragma unroll

@@ -174,11 +174,7 @@ __global__ void silu_mul_kernel(short* __restrict__ out,
     short8v u = *(const short8v*)(in + t * 2 * I + I + i);
     short8v o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float gf = bf2f(g[j]);
-      float s = gf / (1.f + __expf(-gf));
-      o[j] = f2bf(s * bf2f(u[j]));
-    }
+    for (int j = 0; j < 8; ++j) o[j] = swiglu_bf16(g[j], u[j]);
     *(short8v*)(out + t * I + i) = o;
   }
 }
