@@ -122,7 +122,13 @@ class LlamaMLP(nn.Module):
         # gather, so the per-rank weight is itself a [2*I_rank, K] gate_up
         gup = self.gate_up_proj
         assert gup.bias is None and not gup.gather_output
-        return self.down_proj(ops.linear_swiglu(x, gup.weight))
+        if gup.weight_q is not None:
+            act = ops.linear_swiglu_w8a16(
+                x, gup.weight_q, gup.weight_scale, gup.weight
+            )
+        else:
+            act = ops.linear_swiglu(x, gup.weight)
+        return self.down_proj(act)
 
 
 class LlamaLayer(nn.Module):

@@ -323,3 +323,75 @@ def linear_swiglu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
             ext.gemm_skinny_swiglu_bf16(out, x, weight)
             return out
     return silu_mul(linear_bf16(x, weight))
+
+
+# ---------------------------------------------------------------------------
+# FP8 weight-only (W8A16) projections — opt-in, see dts_amd/models/quant.py
+# ---------------------------------------------------------------------------
+
+def _w8_skinny(x: torch.Tensor, w_q: torch.Tensor) -> bool:
+    """Whether (x, w_q) runs the FP8 skinny GEMM: the bf16 skinny
+    conditions (there is no FP8 GEMV — the skinny kernel takes M = 1..16)."""
+    return (
+        x.is_cuda
+        and x.dtype == torch.bfloat16
+        and x.dim() == 2
+        and x.stride(1) == 1
+        and x.shape[1] % 512 == 0
+        and 1 <= x.shape[0] <= 16
+        and w_q.is_contiguous()
+    )
+
+
+def linear_w8a16(
+    x: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, w_deq: torch.Tensor
+) -> torch.Tensor:
+    """y = x @ W^T for a quantised linear: w_q [N, K] FP8 e4m3fn with fp32
+    per-row scales w_scale [N], and w_deq the SAME matrix dequantised into
+    the model dtype (exact for the project's power-of-two scales).
+
+    Decode batches (M<=16, bf16, K%512==0) stream the FP8 copy — half the
+    bytes — through the W8A16 skinny GEMM; everything else (prefill through
+    hipBLASLt, CPU) is linear_bf16 on w_deq, i.e. the same matrix."""
+    if _w8_skinny(x, w_q):
+        ext = _require_hip()
+        if ext is not None:
+            out = torch.empty(
+                (x.shape[0], w_q.shape[0]), dtype=x.dtype, device=x.device
+            )
+            ext.gemm_skinny_w8_bf16(out, x, w_q, w_scale)
+            return out
+    return linear_bf16(x, w_deq)
+
+
+# Largest M at which the fused SwiGLU epilogue replaces GEMM + silu_mul.
+# Measured on FP8 bytes (Llama-3-8B gate_up, GEMM at the committed tile /
+# unroll rules, profiles/microbench_fp8_skinny_rules.jsonl; GEMM + silu_mul
+# -> fused, us): M=1 26.2 -> 26.1, M=4 30.3 -> 28.7, M=8 32.4 -> 30.7, M=16
+# 34.9 -> 36.3. The opposite of the bf16 rule (fused from M >= 8): the GEMM
+# is short enough here that the silu_mul launch shows at every M, while at
+# M=16 the plain GEMM's four tiles per workgroup beat the fused kernel's
+# fixed two. M = 9..15 is not measured and takes the two-kernel path.
+_W8_SWIGLU_MAX_M = 8
+
+
+def linear_swiglu_w8a16(
+    x: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, w_deq: torch.Tensor
+) -> torch.Tensor:
+    """silu_mul(linear_w8a16(...)) for a quantised fused gate_up weight
+    [gate ; up] of shape [2I, K]; returns [M, I]. The fused epilogue is
+    bit-identical to the two-kernel path, so the threshold is a pure
+    performance choice."""
+    if (
+        _w8_skinny(x, w_q)
+        and x.shape[0] <= _W8_SWIGLU_MAX_M
+        and w_q.shape[0] % 32 == 0
+    ):
+        ext = _require_hip()
+        if ext is not None:
+            out = torch.empty(
+                (x.shape[0], w_q.shape[0] // 2), dtype=x.dtype, device=x.device
+            )
+            ext.gemm_skinny_swiglu_w8_bf16(out, x, w_q, w_scale)
+            return out
+    return silu_mul(linear_w8a16(x, w_q, w_scale, w_deq))

@@ -32,6 +32,7 @@ def build(verbose: bool = True) -> Path:
         str(HIP_DIR / "sampling.hip"),
         str(HIP_DIR / "gemv.hip"),
         str(HIP_DIR / "gemm_skinny.hip"),
+        str(HIP_DIR / "gemm_skinny_fp8.hip"),
     ]
     module = load(
         name="_dts_hip",

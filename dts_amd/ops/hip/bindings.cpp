@@ -37,6 +37,11 @@ void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
                              torch::Tensor w);
 void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                         torch::Tensor counts, torch::Tensor offsets);
+void gemm_skinny_w8_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w_q,
+                         torch::Tensor scale, int64_t tiles_per_wg,
+                         int64_t unroll);
+void gemm_skinny_swiglu_w8_bf16(torch::Tensor out, torch::Tensor x,
+                                torch::Tensor w_q, torch::Tensor scale);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
@@ -73,4 +78,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out[M,I] = silu(x Wg^T) * (x Wu^T), w = [Wg; Wu]");
   m.def("moe_grouped_linear", &moe_grouped_linear,
         "grouped per-expert skinny GEMM (capture-safe MoE decode)");
+  m.def("gemm_skinny_w8_bf16", &gemm_skinny_w8_bf16,
+        "W8A16 skinny-M (M<=16) GEMM: FP8 e4m3fn weights [N,K] with an fp32 "
+        "per-row scale [N], bf16 x/out, fp32 accumulation; tiles_per_wg and "
+        "unroll as for gemm_skinny_bf16",
+        py::arg("out"), py::arg("x"), py::arg("w_q"), py::arg("scale"),
+        py::arg("tiles_per_wg") = 0, py::arg("unroll") = 0);
+  m.def("gemm_skinny_swiglu_w8_bf16", &gemm_skinny_swiglu_w8_bf16,
+        "W8A16 gate_up GEMM with fused SwiGLU epilogue: w_q = [Wg; Wu], "
+        "gate rows scale by scale[n], up rows by scale[I+n]");
 }

@@ -198,6 +198,13 @@ def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
     return (torch.nn.functional.silu(gate.float()) * up.float()).to(gate_up.dtype)
 
 
+def linear_w8a16(x: torch.Tensor, w_q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """Numerics oracle of the W8A16 GEMM: FP8 weights [N, K] with an fp32
+    per-row scale [N]; fp32 product, scale applied to the sum, one
+    rounding to x.dtype."""
+    return ((x.float() @ w_q.float().T) * scale.float()).to(x.dtype)
+
+
 def gelu(x: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.gelu(x.float(), approximate="tanh").to(x.dtype)
 

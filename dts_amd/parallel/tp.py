@@ -59,6 +59,14 @@ def _init_weight(out_f: int, in_f: int, dtype, generator=None, device="cpu") -> 
     return w.to(dtype)
 
 
+def _init_weight_quant(lin: nn.Module) -> None:
+    """Empty slots for the opt-in FP8 copy of the weight (weight_q [N, K]
+    e4m3fn + weight_scale [N] fp32), filled by models/quant.py. While they
+    are None the layer is the plain bf16 linear."""
+    lin.register_buffer("weight_q", None, persistent=False)
+    lin.register_buffer("weight_scale", None, persistent=False)
+
+
 class ColumnParallelLinear(nn.Module):
     """Weight [out, in] sharded over `out`; output stays sharded."""
 
@@ -77,11 +85,15 @@ class ColumnParallelLinear(nn.Module):
             if bias
             else None
         )
+        _init_weight_quant(self)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from dts_amd import ops
 
-        y = ops.linear_bf16(x, self.weight)
+        if self.weight_q is not None:
+            y = ops.linear_w8a16(x, self.weight_q, self.weight_scale, self.weight)
+        else:
+            y = ops.linear_bf16(x, self.weight)
         if self.bias is not None:
             y = y + self.bias
         if self.gather_output:
@@ -106,11 +118,15 @@ class RowParallelLinear(nn.Module):
             if bias
             else None
         )
+        _init_weight_quant(self)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from dts_amd import ops
 
-        y = ops.linear_bf16(x, self.weight)
+        if self.weight_q is not None:
+            y = ops.linear_w8a16(x, self.weight_q, self.weight_scale, self.weight)
+        else:
+            y = ops.linear_bf16(x, self.weight)
         y = self.tp.all_reduce(y)
         if self.bias is not None:
             y = y + self.bias

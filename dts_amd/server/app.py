@@ -226,6 +226,9 @@ def main() -> None:
                    help="local HF tokenizers JSON (default: synthetic)")
     p.add_argument("--weights", default=None,
                    help="HF-layout safetensors dir (default: random-init)")
+    p.add_argument("--weight-quant", default=None, choices=["fp8"],
+                   help="weight-only quantisation of the Llama projections "
+                        "(default: none, or DTS_WEIGHT_QUANT)")
     args = p.parse_args()
 
     def factory() -> LLM:
@@ -239,6 +242,7 @@ def main() -> None:
             device=device,
             tokenizer_path=args.tokenizer,
             weights_path=args.weights,
+            weight_quant=args.weight_quant,
         )
         backend = LocalBackend.single(engine, name=args.model)
         return LLM(backend, default_model=args.model)

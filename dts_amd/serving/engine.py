@@ -68,8 +68,19 @@ class ServingEngine:
         model: Optional[object] = None,
         tokenizer_path: Optional[str] = None,
         weights_path: Optional[str] = None,
+        weight_quant: Optional[str] = None,
     ) -> None:
         self.spec: ModelSpec = get_model_spec(model_name)
+        # opt-in weight-only quantisation (models/quant.py); the
+        # environment variable selects it where the caller cannot pass the
+        # keyword (the benchmark)
+        if weight_quant is None:
+            weight_quant = os.environ.get("DTS_WEIGHT_QUANT") or None
+        if weight_quant not in (None, "fp8"):
+            raise ValueError(
+                f"unknown weight_quant {weight_quant!r} (supported: 'fp8')"
+            )
+        self.weight_quant = weight_quant
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         if dtype is None:
@@ -101,6 +112,14 @@ class ServingEngine:
                     )
             else:
                 self.model.random_init(seed=weight_seed)
+        # after load/init and BEFORE the KV pool is sized from free memory:
+        # the FP8 copies are extra weight bytes the pool must leave room for
+        if weight_quant is not None and (
+            getattr(self.model, "weight_quant", None) != weight_quant
+        ):
+            from dts_amd.models.quant import quantize_model_
+
+            quantize_model_(self.model, weight_quant)
 
         kv_heads = getattr(self.model, "num_kv_heads_local", None)
         if kv_heads is None:
@@ -676,6 +695,7 @@ class ServingEngine:
             "free_blocks": src.num_free(),
             "steps": self.steps,
             "graph_steps": self.graph_steps,
+            "weight_quant": self.weight_quant,
             "tokens_sampled": self.tokens_sampled,
             "tokens_prefilled": self.tokens_prefilled,
             "native_scheduler": type(self.scheduler).__name__ == "NativeScheduler",

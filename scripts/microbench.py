@@ -165,7 +165,81 @@ def kernel_probes(ext):
             del kcs, vcs
 
 
+def fp8_kernel_probes(ext):
+    """W8A16 skinny GEMM on the five Llama-3-8B shapes: tiles-per-workgroup
+    and unroll sweeps, the fused SwiGLU crossover, and the bf16 kernel's
+    auto dispatch on the same shape in the same process. The yardstick is
+    bytes: TB/s counts the weight bytes each dtype really moves. Weights
+    cycle through enough copies to exceed the 256 MB Infinity Cache, as in
+    kernel_probes (FP8 copies are half the size, so there are more)."""
+    dev = "cuda"
+    bf16 = torch.bfloat16
+    shapes = (
+        ("qkv", 4096, 6144),
+        ("o", 4096, 4096),
+        ("gate_up", 4096, 28672),
+        ("down", 14336, 4096),
+        ("lm_head", 4096, 128256),
+    )
+    for name, K, N in shapes:
+        copies = max(2, min(32, (512 << 20) // (N * K) + 1))
+        ws = []
+        for _ in range(copies):  # finite e4m3 codes, random sign
+            c = torch.randint(0, 127, (N, K), dtype=torch.uint8, device=dev)
+            c += torch.randint(0, 2, (N, K), dtype=torch.uint8, device=dev) * 128
+            ws.append(c.view(torch.float8_e4m3fn))
+        del c
+        scale = torch.rand(N, device=dev) + 0.5
+        copies16 = max(2, min(8, (1 << 30) // (N * K * 2) + 1))
+        ws16 = [torch.randn(N, K, dtype=bf16, device=dev) for _ in range(copies16)]
+        for M in (1, 4, 8, 16):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            out = torch.empty(M, N, dtype=bf16, device=dev)
+            rec = {"probe": f"skinny_w8_{name}_M{M}_K{K}_N{N}", "copies": copies}
+            for nt in (1, 2, 4):
+                for ku in (4, 8):
+                    t = _time_us(
+                        lambda i: ext.gemm_skinny_w8_bf16(
+                            out, x, ws[i], scale, tiles_per_wg=nt, unroll=ku
+                        ),
+                        copies,
+                    )
+                    rec[f"nt{nt}_ku{ku}_us"] = round(t, 1)
+                    rec[f"nt{nt}_ku{ku}_TBps"] = round(N * K / t / 1e6, 2)
+            t = _time_us(
+                lambda i: ext.gemm_skinny_w8_bf16(out, x, ws[i], scale), copies
+            )
+            rec["auto_us"] = round(t, 1)
+            rec["auto_TBps"] = round(N * K / t / 1e6, 2)
+            t = _time_us(lambda i: ext.gemm_skinny_bf16(out, x, ws16[i]), copies16)
+            rec["bf16_auto_us"] = round(t, 1)
+            rec["bf16_auto_TBps"] = round(N * K * 2 / t / 1e6, 2)
+            if name == "gate_up":
+                act = torch.empty(M, N // 2, dtype=bf16, device=dev)
+
+                def two_kernels(i):
+                    ext.gemm_skinny_w8_bf16(out, x, ws[i], scale)
+                    ext.silu_mul(act, out)
+
+                rec["gemm_auto_plus_silu_mul_us"] = round(
+                    _time_us(two_kernels, copies), 1
+                )
+                t = _time_us(
+                    lambda i: ext.gemm_skinny_swiglu_w8_bf16(act, x, ws[i], scale),
+                    copies,
+                )
+                rec["fused_swiglu_us"] = round(t, 1)
+                rec["fused_swiglu_TBps"] = round(N * K / t / 1e6, 2)
+            print(json.dumps(rec), flush=True)
+        del ws, ws16
+
+
 def main():
+    if "--fp8-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        fp8_kernel_probes(_hip_ext_loader.load())
+        return
     if "--kernels-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
 
