@@ -18,6 +18,7 @@
 // Semantics match dts_amd/ops/torch_ref.py attn_*_paged.
 
 #include "common.h"
+#include "kv_cache.h"
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <unordered_map>
@@ -26,6 +27,29 @@
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+
+// ---------------------------------------------------------------------------
+// FP8 KV cache (opt-in). Every kernel below takes the cache element type as
+// its last template parameter KV: short = bf16 (the default, and the code
+// the bf16 instantiations compile is the code they always compiled), or
+// unsigned char = OCP e4m3fn codes with scale 1.0. Every finite e4m3 value
+// is a bf16 value, so the load-side conversions are exact and everything
+// after the load is the bf16 kernel's arithmetic.
+// ---------------------------------------------------------------------------
+
+// 8 e4m3 bytes (two dwords) -> 8 bf16, element order = byte order
+DEV bf16x8 kv_deq8(u32x2 w) {
+  union { bf16x2 p[4]; bf16x8 v; } c;
+  c.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], 1.0f, false);
+  c.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], 1.0f, true);
+  c.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], 1.0f, false);
+  c.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], 1.0f, true);
+  return c.v;
+}
 
 // ---------------------------------------------------------------------------
 // Decode
@@ -37,14 +61,14 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // (m, l, o) into the fp32 workspace, combined by attn_decode_combine.
 // S is FIXED per launch so decode steps stay hipGraph-capturable with
 // varying kv_lens; splits past a short sequence's pages exit immediately.
-template <int G, int D>
+template <int G, int D, typename KV = short>
 __global__ void __launch_bounds__(256)
 attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
                    float* __restrict__ ws_l,  // [B, Hkv, S, G]
                    float* __restrict__ ws_o,  // [B, Hkv, S, G, D]
                    const short* __restrict__ q,      // [B, Hq, D]
-                   const short* __restrict__ kcache, // [N, Hkv, BS, D]
-                   const short* __restrict__ vcache,
+                   const KV* __restrict__ kcache, // [N, Hkv, BS, D]
+                   const KV* __restrict__ vcache,
                    const int* __restrict__ block_tables, // [B, max_blocks]
                    const int* __restrict__ kv_lens,      // [B]
                    int max_blocks, int Hkv, float scale, long q_tstride) {
@@ -106,9 +130,9 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
 
   for (int page = page_lo + wave; page < page_hi; page += NWAVE) {
     const long blk = bt[page];
-    const short* kbase =
+    const KV* kbase =
         kcache + ((blk * Hkv + kvh) * BS) * (long)D;
-    const short* vbase =
+    const KV* vbase =
         vcache + ((blk * Hkv + kvh) * BS) * (long)D;
     const int valid = min(BS, kv_len - page * BS);
 
@@ -116,8 +140,41 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
     float partial[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) partial[g] = 0.f;
-    if (key_of_lane < valid) {
-      const short* kp = kbase + key_of_lane * D + c * DPL;
+    if constexpr (sizeof(KV) == 1) {
+      // FP8: the lane's DPL codes are 32 B (D=128) / 16 B (D=64): 16 B
+      // loads, four codes per dword converted two at a time; the pairing
+      // and the order of the fp32 sums are the bf16 branch's.
+      if (key_of_lane < valid) {
+        const KV* kp = kbase + key_of_lane * D + c * DPL;
+        unsigned int kw[DPL / 4];
+#pragma unroll
+        for (int x = 0; x < DPL / 16; ++x) {
+          const u32x4 t = ((const u32x4*)kp)[x];
+#pragma unroll
+          for (int y = 0; y < 4; ++y) kw[4 * x + y] = t[y];
+        }
+#pragma unroll
+        for (int w = 0; w < DPL / 4; ++w) {
+          // the builtin's word-select must be a literal
+          const f32x2 kf[2] = {
+              __builtin_amdgcn_cvt_pk_f32_fp8((int)kw[w], false),
+              __builtin_amdgcn_cvt_pk_f32_fp8((int)kw[w], true)};
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int i = 2 * w + h;  // the bf16 branch's pair index
+            float k0 = kf[h][0];
+            float k1 = kf[h][1];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+              float q0 = bf2f((short)(qp_[g][i] & 0xffff));
+              float q1 = bf2f((short)((qp_[g][i] >> 16) & 0xffff));
+              partial[g] += q0 * k0 + q1 * k1;
+            }
+          }
+        }
+      }
+    } else if (key_of_lane < valid) {
+      const KV* kp = kbase + key_of_lane * D + c * DPL;
 #pragma unroll
       for (int i = 0; i < DPL / 2; ++i) {
         int kw = ((const int*)kp)[i];
@@ -150,10 +207,17 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
 #pragma unroll
     for (int j = 0; j < BS; ++j) {
       if (j < valid) {
-        if constexpr (DPV == 2)
+        if constexpr (sizeof(KV) == 1) {
+          // FP8: DPV codes per row = 2 B / 1 B, in the word's low bytes
+          if constexpr (DPV == 2)
+            vw[j] = (int)*(const unsigned short*)(vbase + j * D + 2 * lane);
+          else
+            vw[j] = (int)*(const unsigned char*)(vbase + j * D + lane);
+        } else if constexpr (DPV == 2) {
           vw[j] = *(const int*)(vbase + j * D + 2 * lane);
-        else
+        } else {
           vw[j] = (int)*(const unsigned short*)(vbase + j * D + lane);
+        }
       } else {
         vw[j] = 0;
       }
@@ -180,11 +244,20 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
           psum += p[j];
         }
         lsum[g] += psum;
+        if constexpr (sizeof(KV) == 1) {
 #pragma unroll
-        for (int j = 0; j < BS; ++j) {
-          o[g][0] += p[j] * bf2f((short)(vw[j] & 0xffff));
-          if constexpr (DPV == 2)
-            o[g][1] += p[j] * bf2f((short)((vw[j] >> 16) & 0xffff));
+          for (int j = 0; j < BS; ++j) {
+            const f32x2 vf = __builtin_amdgcn_cvt_pk_f32_fp8(vw[j], false);
+            o[g][0] += p[j] * vf[0];
+            if constexpr (DPV == 2) o[g][1] += p[j] * vf[1];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < BS; ++j) {
+            o[g][0] += p[j] * bf2f((short)(vw[j] & 0xffff));
+            if constexpr (DPV == 2)
+              o[g][1] += p[j] * bf2f((short)((vw[j] >> 16) & 0xffff));
+          }
         }
       }
     }
@@ -559,14 +632,14 @@ attn_prefill_kernel_v2(short* __restrict__ out,      // [Tq, Hq, D]
 // more workgroups per CU).
 // ---------------------------------------------------------------------------
 
-template <int G, int D, int KSTEP>
+template <int G, int D, int KSTEP, typename KV = short>
 __global__ void __launch_bounds__(256)
 attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
                        const short* __restrict__ q,  // [Tq, Hq, D]
                        const int* __restrict__ cu_q, // [P+1]
                        const long* __restrict__ q_pos, // [Tq]
-                       const short* __restrict__ kcache,
-                       const short* __restrict__ vcache,
+                       const KV* __restrict__ kcache,
+                       const KV* __restrict__ vcache,
                        const int* __restrict__ block_tables,
                        const int* __restrict__ kv_lens, int max_blocks,
                        int Hkv, float scale, long q_tstride) {
@@ -641,8 +714,16 @@ attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
           const long blk = bt[kglob / BS];
           const long off =
               ((blk * Hkv + kvh) * BS + kglob % BS) * (long)D + d0;
-          *(bf16x8*)(&k_lds[key][d0]) = *(const bf16x8*)(kcache + off);
-          *(bf16x8*)(&v_lds[key][d0]) = *(const bf16x8*)(vcache + off);
+          if constexpr (sizeof(KV) == 1) {
+            // FP8: 8 B per tensor, converted to the same 16 B of bf16
+            *(bf16x8*)(&k_lds[key][d0]) =
+                kv_deq8(*(const u32x2*)(kcache + off));
+            *(bf16x8*)(&v_lds[key][d0]) =
+                kv_deq8(*(const u32x2*)(vcache + off));
+          } else {
+            *(bf16x8*)(&k_lds[key][d0]) = *(const bf16x8*)(kcache + off);
+            *(bf16x8*)(&v_lds[key][d0]) = *(const bf16x8*)(vcache + off);
+          }
         } else {
           const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
           *(bf16x8*)(&k_lds[key][d0]) = z;
@@ -823,14 +904,14 @@ attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
 // col' = col ^ ((key & 7) << 3), applied identically at the cooperative
 // store and every read — spreads the b128 B-frag lane groups across bank
 // slots. A/B-selectable per call (scripts/prefill_probe.py).
-template <int G, int D, bool SWZ>
+template <int G, int D, bool SWZ, typename KV = short>
 __global__ void __launch_bounds__(256)
 attn_prefill_kernel(short* __restrict__ out,      // [Tq, Hq, D]
                     const short* __restrict__ q,  // [Tq, Hq, D]
                     const int* __restrict__ cu_q, // [P+1]
                     const long* __restrict__ q_pos, // [Tq]
-                    const short* __restrict__ kcache,
-                    const short* __restrict__ vcache,
+                    const KV* __restrict__ kcache,
+                    const KV* __restrict__ vcache,
                     const int* __restrict__ block_tables,
                     const int* __restrict__ kv_lens, int max_blocks, int Hkv,
                     float scale, long q_tstride) {
@@ -926,12 +1007,18 @@ attn_prefill_kernel(short* __restrict__ out,      // [Tq, Hq, D]
         const int dst = swz_col(key, d0);
         if (kglob < kv_len) {
           const long blk = bt[page];
-          const short* kp =
+          const KV* kp =
               kcache + ((blk * Hkv + kvh) * BS + koff) * (long)D + d0;
-          const short* vp =
+          const KV* vp =
               vcache + ((blk * Hkv + kvh) * BS + koff) * (long)D + d0;
-          *(bf16x8*)(&k_lds[key][dst]) = *(const bf16x8*)kp;
-          *(bf16x8*)(&v_lds[key][dst]) = *(const bf16x8*)vp;
+          if constexpr (sizeof(KV) == 1) {
+            // FP8: 8 B per tensor, converted to the same 16 B of bf16
+            *(bf16x8*)(&k_lds[key][dst]) = kv_deq8(*(const u32x2*)kp);
+            *(bf16x8*)(&v_lds[key][dst]) = kv_deq8(*(const u32x2*)vp);
+          } else {
+            *(bf16x8*)(&k_lds[key][dst]) = *(const bf16x8*)kp;
+            *(bf16x8*)(&v_lds[key][dst]) = *(const bf16x8*)vp;
+          }
         } else {
           bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
           *(bf16x8*)(&k_lds[key][dst]) = z;
@@ -1085,6 +1172,7 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q,
   const int G = Hq / Hkv;
   const int max_blocks = block_tables.size(1);
   TORCH_CHECK(kcache.size(2) == 16, "block_size must be 16");
+  const bool fp8 = kv_cache_is_fp8(kcache, vcache);
   TORCH_CHECK(block_tables.scalar_type() == torch::kInt32);
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == D, "q heads must be dense");
   TORCH_CHECK(out.is_contiguous(), "out must be contiguous");
@@ -1130,16 +1218,19 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q,
   dim3 grid(B, Hkv, S);
   dim3 block(256);
   auto stream = c10::hip::getCurrentHIPStream();
+#define DECODE_LAUNCH(g, d, kv)                                              \
+  hipLaunchKernelGGL((attn_decode_kernel<g, d, kv>), grid, block, 0, stream, \
+                     (float*)ws_m.data_ptr(), (float*)ws_l.data_ptr(),       \
+                     (float*)ws_o.data_ptr(), (const short*)q.data_ptr(),    \
+                     (const kv*)kcache.data_ptr(),                           \
+                     (const kv*)vcache.data_ptr(),                           \
+                     (const int*)block_tables.data_ptr(),                    \
+                     (const int*)kv_lens.data_ptr(), max_blocks, Hkv,        \
+                     (float)scale, q_tstride)
 #define DECODE_CASE(g, d)                                                    \
   do {                                                                       \
-    hipLaunchKernelGGL((attn_decode_kernel<g, d>), grid, block, 0, stream,   \
-                       (float*)ws_m.data_ptr(), (float*)ws_l.data_ptr(),     \
-                       (float*)ws_o.data_ptr(), (const short*)q.data_ptr(),  \
-                       (const short*)kcache.data_ptr(),                      \
-                       (const short*)vcache.data_ptr(),                      \
-                       (const int*)block_tables.data_ptr(),                  \
-                       (const int*)kv_lens.data_ptr(), max_blocks, Hkv,      \
-                       (float)scale, q_tstride);                             \
+    if (fp8) DECODE_LAUNCH(g, d, unsigned char);                             \
+    else DECODE_LAUNCH(g, d, short);                                         \
     hipLaunchKernelGGL((attn_decode_combine<d>), dim3(B, Hq), dim3(256), 0,  \
                        stream, (short*)out.data_ptr(),                       \
                        (const float*)ws_m.data_ptr(),                        \
@@ -1152,6 +1243,7 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q,
   else if (D == 64 && G == 1) DECODE_CASE(1, 64);
   else TORCH_CHECK(false, "unsupported decode attn shape D=", D, " G=", G);
 #undef DECODE_CASE
+#undef DECODE_LAUNCH
   HIP_CHECK_LAST();
 }
 
@@ -1173,6 +1265,12 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
     }();
     swz = (env_v >= 0) ? env_v : 5;
   }
+  // FP8 cache: v1 (0) and v5 (4/5) have a converting tile load; the
+  // ablation variants read bf16 only.
+  const bool fp8 = kv_cache_is_fp8(kcache, vcache);
+  TORCH_CHECK(!fp8 || swz == 0 || swz == 4 || swz == 5,
+              "prefill variant ", swz, " (DTS_PREFILL_V) does not support an "
+              "FP8 KV cache; use 0, 4 or 5");
   const int Hq = q.size(1), D = q.size(2);
   const int Hkv = kcache.size(1);
   const int G = Hq / Hkv;
@@ -1261,12 +1359,39 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                          (const int*)kv_lens.data_ptr(), max_blocks, Hkv,     \
                          (float)scale, q_tstride);                            \
   } while (0)
-  if (D == 128 && G == 4) PREFILL_CASE(4, 128);
+#define PREFILL_LAUNCH_FP8(kern)                                              \
+  hipLaunchKernelGGL(kern, grid, block, 0, stream, (short*)out.data_ptr(),    \
+                     (const short*)q.data_ptr(), (const int*)cu_q.data_ptr(), \
+                     (const long*)q_pos.data_ptr(),                           \
+                     (const unsigned char*)kcache.data_ptr(),                 \
+                     (const unsigned char*)vcache.data_ptr(),                 \
+                     (const int*)block_tables.data_ptr(),                     \
+                     (const int*)kv_lens.data_ptr(), max_blocks, Hkv,         \
+                     (float)scale, q_tstride)
+#define PREFILL_CASE_FP8(g, d)                                                \
+  do {                                                                        \
+    if (swz == 4)                                                             \
+      PREFILL_LAUNCH_FP8((attn_prefill_kernel_v5<g, d, 32, unsigned char>));  \
+    else if (swz == 5)                                                        \
+      PREFILL_LAUNCH_FP8((attn_prefill_kernel_v5<g, d, 64, unsigned char>));  \
+    else                                                                      \
+      PREFILL_LAUNCH_FP8((attn_prefill_kernel<g, d, false, unsigned char>));  \
+  } while (0)
+  if (fp8) {
+    if (D == 128 && G == 4) PREFILL_CASE_FP8(4, 128);
+    else if (D == 128 && G == 8) PREFILL_CASE_FP8(8, 128);
+    else if (D == 128 && G == 1) PREFILL_CASE_FP8(1, 128);
+    else if (D == 128 && G == 2) PREFILL_CASE_FP8(2, 128);
+    else if (D == 64 && G == 1) PREFILL_CASE_FP8(1, 64);
+    else TORCH_CHECK(false, "unsupported prefill shape G=", G, " D=", D);
+  } else if (D == 128 && G == 4) PREFILL_CASE(4, 128);
   else if (D == 128 && G == 8) PREFILL_CASE(8, 128);
   else if (D == 128 && G == 1) PREFILL_CASE(1, 128);
   else if (D == 128 && G == 2) PREFILL_CASE(2, 128);
   else if (D == 64 && G == 1) PREFILL_CASE(1, 64);
   else TORCH_CHECK(false, "unsupported prefill shape G=", G, " D=", D);
 #undef PREFILL_CASE
+#undef PREFILL_CASE_FP8
+#undef PREFILL_LAUNCH_FP8
   HIP_CHECK_LAST();
 }

@@ -50,14 +50,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul", &silu_mul, "SwiGLU activation (bf16)");
   m.def("layernorm", &layernorm, "LayerNorm (bf16, GPT-2 path)");
   m.def("rope_kv_append", &rope_kv_append,
-        "fused rotate-half RoPE + paged KV append (bf16)");
-  m.def("kv_append", &kv_append, "paged KV append without RoPE (bf16)");
+        "fused rotate-half RoPE + paged KV append (bf16 q/k/v; bf16 or FP8 "
+        "e4m3fn cache)");
+  m.def("kv_append", &kv_append,
+        "paged KV append without RoPE (bf16 k/v; bf16 or FP8 e4m3fn cache)");
   m.def("attn_decode_paged", &attn_decode_paged,
-        "paged GQA decode attention (bf16, wave-per-kv-head)");
+        "paged GQA decode attention (bf16 q/out, bf16 or FP8 e4m3fn cache)");
   m.def("attn_prefill_paged", &attn_prefill_paged,
-        "paged causal prefill attention (bf16, MFMA)", py::arg("out"),
-        py::arg("q"), py::arg("cu_q"), py::arg("q_pos"), py::arg("kcache"),
-        py::arg("vcache"), py::arg("block_tables"), py::arg("kv_lens"),
+        "paged causal prefill attention (bf16 MFMA; bf16 or FP8 e4m3fn cache)",
+        py::arg("out"), py::arg("q"), py::arg("cu_q"), py::arg("q_pos"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("block_tables"),
+        py::arg("kv_lens"),
         py::arg("scale"), py::arg("swz") = -1);
   m.def("top_p_sample", &top_p_sample,
         "fused temperature softmax + top-p sampling (sort-free)");

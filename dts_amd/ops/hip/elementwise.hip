@@ -9,6 +9,7 @@
 // silu_mul) — numerics tests compare against that fp32 reference.
 
 #include "common.h"
+#include "kv_cache.h"
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
@@ -184,17 +185,19 @@ __global__ void silu_mul_kernel(short* __restrict__ out,
 //   q: [T, Hq, D] bf16 (rotated in place)
 //   k: [T, Hk, D] bf16 (rotated in place, then written to k_cache)
 //   v: [T, Hk, D] bf16 (written to v_cache)
-//   cos/sin: [P, D/2] fp32;  caches: [N, Hk, BS, D] bf16
+//   cos/sin: [P, D/2] fp32;  caches: [N, Hk, BS, D] bf16, or (KV =
+//   unsigned char) FP8 e4m3fn codes of the same values, scale 1.0
 //   slot_mapping: [T] int64 flat slot  (block = slot/BS, off = slot%BS)
 // One wave per (token, head); lane l owns dims {l, l+D/2} when D==128
 // (pairs 2 per lane via the rotate-half pairing), fp32 math.
 // ---------------------------------------------------------------------------
 
+template <typename KV>
 __global__ void rope_kv_append_kernel(
     short* __restrict__ q, short* __restrict__ k, const short* __restrict__ v,
     const long* __restrict__ positions, const float* __restrict__ cos_t,
-    const float* __restrict__ sin_t, short* __restrict__ k_cache,
-    short* __restrict__ v_cache, const long* __restrict__ slots, int T, int Hq,
+    const float* __restrict__ sin_t, KV* __restrict__ k_cache,
+    KV* __restrict__ v_cache, const long* __restrict__ slots, int T, int Hq,
     int Hk, int D, int BS, long cache_head_stride, long cache_block_stride,
     int do_rope, long q_tstride, long k_tstride, long v_tstride) {
   // q/k/v may be row-strided VIEWS of a fused qkv projection (token-row
@@ -230,14 +233,33 @@ __global__ void rope_kv_append_kernel(
     int kvh = is_v ? (h - Hq - Hk) : (h - Hq);
     const short* src = is_v ? v + (long)t * v_tstride + (long)kvh * D
                             : k + (long)t * k_tstride + (long)kvh * D;
-    short* cache = is_v ? v_cache : k_cache;
+    KV* cache = is_v ? v_cache : k_cache;
     long slot = slots[t];
     long block = slot / BS, off = slot % BS;
-    short* dst = cache + block * cache_block_stride + kvh * cache_head_stride +
-                 off * D;
-    for (int i = lane * 2; i < D; i += WAVE * 2) {
-      // k was just rotated by THIS wave for k-units; safe (no cross-wave dep)
-      *(int*)(dst + i) = *(const int*)(src + i);
+    KV* dst = cache + block * cache_block_stride + kvh * cache_head_stride +
+              off * D;
+    if constexpr (sizeof(KV) == 1) {
+      // FP8: code = RNE_e4m3fn(clamp(x, -448, 448)) of the bf16 value the
+      // bf16 cache would hold (k: the rotated value AFTER its bf16 round
+      // above). The clamp is required: the conversion gives NaN above 464.
+      // 4 dims per lane so the 4 codes go out as one 32-bit store.
+      for (int i = lane * 4; i < D; i += WAVE * 4) {
+        int w0 = *(const int*)(src + i);
+        int w1 = *(const int*)(src + i + 2);
+        auto sat = [](int u) {
+          return fminf(fmaxf(bf2f((short)(u & 0xffff)), -448.f), 448.f);
+        };
+        float f0 = sat(w0), f1 = sat(w0 >> 16);
+        float f2 = sat(w1), f3 = sat(w1 >> 16);
+        int codes = __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, 0, false);
+        codes = __builtin_amdgcn_cvt_pk_fp8_f32(f2, f3, codes, true);
+        *(int*)(dst + i) = codes;
+      }
+    } else {
+      for (int i = lane * 2; i < D; i += WAVE * 2) {
+        // k was just rotated by THIS wave for k-units; safe (no cross-wave dep)
+        *(int*)(dst + i) = *(const int*)(src + i);
+      }
     }
   }
 }
@@ -311,23 +333,29 @@ void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   check_qkv_layout(q);
   check_qkv_layout(k);
   check_qkv_layout(v);
+  const bool fp8 = kv_cache_is_fp8(k_cache, v_cache);
   int T = q.size(0), Hq = q.size(1), D = q.size(2), Hk = k.size(1);
+  TORCH_CHECK(!fp8 || D % 4 == 0, "FP8 append needs head_dim % 4 == 0");
   int BS = k_cache.size(2);
   long head_stride = k_cache.stride(1), block_stride = k_cache.stride(0);
   int units = T * (Hq + 2 * Hk);
   int waves_per_block = 4;
   int blocks = (units + waves_per_block - 1) / waves_per_block;
-  hipLaunchKernelGGL(rope_kv_append_kernel, dim3(blocks),
-                     dim3(waves_per_block * WAVE), 0,
-                     c10::hip::getCurrentHIPStream(), (short*)q.data_ptr(),
-                     (short*)k.data_ptr(), (const short*)v.data_ptr(),
-                     (const long*)positions.data_ptr(),
-                     (const float*)cos_t.data_ptr(),
-                     (const float*)sin_t.data_ptr(),
-                     (short*)k_cache.data_ptr(), (short*)v_cache.data_ptr(),
-                     (const long*)slots.data_ptr(), T, Hq, Hk, D, BS,
-                     head_stride, block_stride, 1, q.stride(0), k.stride(0),
-                     v.stride(0));
+#define ROPE_APPEND_LAUNCH(kv)                                                \
+  hipLaunchKernelGGL(rope_kv_append_kernel<kv>, dim3(blocks),                 \
+                     dim3(waves_per_block * WAVE), 0,                         \
+                     c10::hip::getCurrentHIPStream(), (short*)q.data_ptr(),   \
+                     (short*)k.data_ptr(), (const short*)v.data_ptr(),        \
+                     (const long*)positions.data_ptr(),                       \
+                     (const float*)cos_t.data_ptr(),                          \
+                     (const float*)sin_t.data_ptr(),                          \
+                     (kv*)k_cache.data_ptr(), (kv*)v_cache.data_ptr(),        \
+                     (const long*)slots.data_ptr(), T, Hq, Hk, D, BS,         \
+                     head_stride, block_stride, 1, q.stride(0), k.stride(0),  \
+                     v.stride(0))
+  if (fp8) ROPE_APPEND_LAUNCH(unsigned char);
+  else ROPE_APPEND_LAUNCH(short);
+#undef ROPE_APPEND_LAUNCH
   HIP_CHECK_LAST();
 }
 
@@ -335,7 +363,9 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
                torch::Tensor v_cache, torch::Tensor slots) {
   // no-rope append (GPT-2 path): reuse the same kernel with Hq = 0 and a
   // null q/rope — implemented by passing k as q with Hq=0.
+  const bool fp8 = kv_cache_is_fp8(k_cache, v_cache);
   int T = k.size(0), Hk = k.size(1), D = k.size(2);
+  TORCH_CHECK(!fp8 || D % 4 == 0, "FP8 append needs head_dim % 4 == 0");
   int BS = k_cache.size(2);
   // positions unused for the copy path, but required by signature — pass
   // slots as positions (never dereferenced for copy-only units when Hq==0
@@ -343,13 +373,17 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
   long head_stride = k_cache.stride(1), block_stride = k_cache.stride(0);
   int units = T * (0 + 2 * Hk);
   int blocks = (units + 3) / 4;
-  hipLaunchKernelGGL(rope_kv_append_kernel, dim3(blocks), dim3(256), 0,
-                     c10::hip::getCurrentHIPStream(), (short*)k.data_ptr(),
-                     (short*)k.data_ptr(), (const short*)v.data_ptr(),
-                     (const long*)slots.data_ptr(), nullptr, nullptr,
-                     (short*)k_cache.data_ptr(), (short*)v_cache.data_ptr(),
-                     (const long*)slots.data_ptr(), T, 0, Hk, D, BS,
-                     head_stride, block_stride, 0, 0, k.stride(0),
-                     v.stride(0));
+#define KV_APPEND_LAUNCH(kv)                                                  \
+  hipLaunchKernelGGL(rope_kv_append_kernel<kv>, dim3(blocks), dim3(256), 0,   \
+                     c10::hip::getCurrentHIPStream(), (short*)k.data_ptr(),   \
+                     (short*)k.data_ptr(), (const short*)v.data_ptr(),        \
+                     (const long*)slots.data_ptr(), nullptr, nullptr,         \
+                     (kv*)k_cache.data_ptr(), (kv*)v_cache.data_ptr(),        \
+                     (const long*)slots.data_ptr(), T, 0, Hk, D, BS,          \
+                     head_stride, block_stride, 0, 0, k.stride(0),            \
+                     v.stride(0))
+  if (fp8) KV_APPEND_LAUNCH(unsigned char);
+  else KV_APPEND_LAUNCH(short);
+#undef KV_APPEND_LAUNCH
   HIP_CHECK_LAST();
 }

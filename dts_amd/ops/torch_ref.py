@@ -87,6 +87,17 @@ def rope_apply(
 # Paged KV append
 # ---------------------------------------------------------------------------
 
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_kv_fp8(x: torch.Tensor) -> torch.Tensor:
+    """The FP8 KV cache's store: OCP float8_e4m3fn at scale 1.0, round to
+    nearest even, saturating at +-448 (+-inf included). The clamp is
+    required: the plain cast gives NaN above 464. NaN in is unspecified.
+    Dequantisation (`.float()` / `.to(bfloat16)`) is exact."""
+    return x.float().clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+
+
 def kv_append(
     k: torch.Tensor,  # [T, Hkv, D]
     v: torch.Tensor,
@@ -97,6 +108,16 @@ def kv_append(
     block_size = k_cache.shape[2]
     blocks = torch.div(slot_mapping, block_size, rounding_mode="floor")
     offs = slot_mapping - blocks * block_size
+    if k_cache.dtype == torch.float8_e4m3fn:
+        # codes are written through a byte view (indexed assignment of FP8
+        # tensors is not available on every device)
+        k_cache.view(torch.uint8)[blocks, :, offs] = quantize_kv_fp8(k).view(
+            torch.uint8
+        )
+        v_cache.view(torch.uint8)[blocks, :, offs] = quantize_kv_fp8(v).view(
+            torch.uint8
+        )
+        return
     k_cache[blocks, :, offs] = k.to(k_cache.dtype)
     v_cache[blocks, :, offs] = v.to(v_cache.dtype)
 

@@ -229,6 +229,10 @@ def main() -> None:
     p.add_argument("--weight-quant", default=None, choices=["fp8"],
                    help="weight-only quantisation of the Llama projections "
                         "(default: none, or DTS_WEIGHT_QUANT)")
+    p.add_argument("--kv-cache-dtype", default=None, choices=["auto", "fp8"],
+                   help="paged KV cache dtype: auto = the model dtype, fp8 = "
+                        "e4m3 at half the bytes (default: auto, or "
+                        "DTS_KV_CACHE_DTYPE)")
     args = p.parse_args()
 
     def factory() -> LLM:
@@ -243,6 +247,7 @@ def main() -> None:
             tokenizer_path=args.tokenizer,
             weights_path=args.weights,
             weight_quant=args.weight_quant,
+            kv_cache_dtype=args.kv_cache_dtype,
         )
         backend = LocalBackend.single(engine, name=args.model)
         return LLM(backend, default_model=args.model)

@@ -69,6 +69,7 @@ class ServingEngine:
         tokenizer_path: Optional[str] = None,
         weights_path: Optional[str] = None,
         weight_quant: Optional[str] = None,
+        kv_cache_dtype: Optional[str] = None,
     ) -> None:
         self.spec: ModelSpec = get_model_spec(model_name)
         # opt-in weight-only quantisation (models/quant.py); the
@@ -81,6 +82,19 @@ class ServingEngine:
                 f"unknown weight_quant {weight_quant!r} (supported: 'fp8')"
             )
         self.weight_quant = weight_quant
+        # opt-in FP8 (e4m3, scale 1.0) paged KV cache: half the bytes per
+        # cached token, so twice the blocks for the same memory. None and
+        # "auto" keep the model dtype. Same precedence as weight_quant.
+        if kv_cache_dtype is None:
+            kv_cache_dtype = os.environ.get("DTS_KV_CACHE_DTYPE") or None
+        if kv_cache_dtype == "auto":
+            kv_cache_dtype = None
+        if kv_cache_dtype not in (None, "fp8"):
+            raise ValueError(
+                f"unknown kv_cache_dtype {kv_cache_dtype!r} "
+                "(supported: 'auto', 'fp8')"
+            )
+        self.kv_cache_dtype = kv_cache_dtype
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         if dtype is None:
@@ -124,6 +138,11 @@ class ServingEngine:
         kv_heads = getattr(self.model, "num_kv_heads_local", None)
         if kv_heads is None:
             kv_heads = self.spec.num_kv_heads
+        if kv_cache_dtype == "fp8":
+            kv_dtype, kv_dtype_bytes = torch.float8_e4m3fn, 1
+        else:
+            kv_dtype = dtype
+            kv_dtype_bytes = 2 if dtype == torch.bfloat16 else 4
         if num_blocks is None:
             if kv_memory_bytes is None:
                 if device.startswith("cuda"):
@@ -140,7 +159,7 @@ class ServingEngine:
                 kv_heads,
                 self.spec.head_dim,
                 block_size,
-                dtype_bytes=2 if dtype == torch.bfloat16 else 4,
+                dtype_bytes=kv_dtype_bytes,
             )
         self.kv_pool = KVCachePool(
             self.spec.num_layers,
@@ -148,7 +167,7 @@ class ServingEngine:
             self.spec.head_dim,
             num_blocks,
             block_size,
-            dtype=dtype,
+            dtype=kv_dtype,
             device=device,
         )
         # last block reserved as the hipGraph pad-row scratch target
@@ -696,6 +715,7 @@ class ServingEngine:
             "steps": self.steps,
             "graph_steps": self.graph_steps,
             "weight_quant": self.weight_quant,
+            "kv_cache_dtype": self.kv_cache_dtype,
             "tokens_sampled": self.tokens_sampled,
             "tokens_prefilled": self.tokens_prefilled,
             "native_scheduler": type(self.scheduler).__name__ == "NativeScheduler",

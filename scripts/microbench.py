@@ -234,7 +234,60 @@ def fp8_kernel_probes(ext):
         del ws, ws16
 
 
+def kv_fp8_probes(ext):
+    """Decode attention on an FP8 (e4m3) paged KV cache against the bf16
+    kernel: the B x kv grid and the 8 cycled caches of kernel_probes, both
+    dtypes in this process, alternating, three rounds each (median). TB/s
+    counts the K/V bytes each dtype really moves."""
+    dev = "cuda"
+    bf16 = torch.bfloat16
+    Hq, Hkv, D, BS = 32, 8, 128, 16
+    layers = 8
+    for B in (1, 6, 16):
+        for kv in (512, 2048, 12288):
+            pages = kv // BS
+            NB = B * pages
+            shape = (NB, Hkv, BS, D)
+            k16 = [torch.randn(shape, dtype=bf16, device=dev) for _ in range(layers)]
+            v16 = [torch.randn(shape, dtype=bf16, device=dev) for _ in range(layers)]
+            # the same values, stored as the append kernel would store them
+            k8 = [t.float().clamp(-448, 448).to(torch.float8_e4m3fn) for t in k16]
+            v8 = [t.float().clamp(-448, 448).to(torch.float8_e4m3fn) for t in v16]
+            bt = torch.randperm(NB, device=dev).to(torch.int32).view(B, pages)
+            kvl = torch.full((B,), kv, dtype=torch.int32, device=dev)
+            kvl -= torch.arange(B, dtype=torch.int32, device=dev) * 3  # ragged
+            q = torch.randn(B, Hq, D, dtype=bf16, device=dev)
+            out = torch.empty_like(q)
+            elems = 2 * int(kvl.sum()) * Hkv * D
+            rec = {"probe": f"attn_decode_kv_fp8_B{B}_kv{kv}",
+                   "kv_MB_bf16": round(elems * 2 / 1e6, 1),
+                   "kv_MB_fp8": round(elems / 1e6, 1)}
+            t16, t8 = [], []
+            for _ in range(3):
+                t16.append(_time_us(
+                    lambda i: ext.attn_decode_paged(
+                        out, q, k16[i], v16[i], bt, kvl, D**-0.5),
+                    layers, reps=1))
+                t8.append(_time_us(
+                    lambda i: ext.attn_decode_paged(
+                        out, q, k8[i], v8[i], bt, kvl, D**-0.5),
+                    layers, reps=1))
+            a, b = sorted(t16)[1], sorted(t8)[1]
+            rec["bf16_us"] = round(a, 1)
+            rec["fp8_us"] = round(b, 1)
+            rec["bf16_TBps"] = round(elems * 2 / a / 1e6, 2)
+            rec["fp8_TBps"] = round(elems / b / 1e6, 2)
+            rec["speedup"] = round(a / b, 3)
+            print(json.dumps(rec), flush=True)
+            del k16, v16, k8, v8
+
+
 def main():
+    if "--kv-fp8-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        kv_fp8_probes(_hip_ext_loader.load())
+        return
     if "--fp8-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
 

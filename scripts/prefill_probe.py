@@ -79,6 +79,56 @@ def probe(N=4096, Hq=32, Hkv=8, D=128, iters=20):
     )
 
 
+def probe_kv_fp8(N=4096, Hq=32, Hkv=8, D=128, iters=20):
+    """FP8 (e4m3) KV cache against the bf16 cache holding the same values,
+    variants 0/4/5, interleaved in one process (two rounds each)."""
+    torch.manual_seed(0)
+    BS = 16
+    n_blocks = N // BS + 2
+    q = torch.randn(N, Hq, D, dtype=torch.bfloat16, device="cuda")
+    caches = {}
+    k8 = torch.randn(n_blocks, Hkv, BS, D, device="cuda").to(torch.float8_e4m3fn)
+    v8 = torch.randn(n_blocks, Hkv, BS, D, device="cuda").to(torch.float8_e4m3fn)
+    caches["fp8"] = (k8, v8)
+    caches["bf16"] = (k8.to(torch.bfloat16), v8.to(torch.bfloat16))
+    bt = torch.arange(1, n_blocks + 1, dtype=torch.int32, device="cuda").unsqueeze(0)
+    kvl = torch.tensor([N], dtype=torch.int32, device="cuda")
+    cu_q = torch.tensor([0, N], dtype=torch.int32, device="cuda")
+    q_pos = torch.arange(N, dtype=torch.long, device="cuda")
+    out = torch.empty_like(q)
+    scale = D ** -0.5
+    flops = 2 * 2 * Hq * (N * N / 2) * D
+    rec = {"probe": f"prefill_attn_kv_fp8_N{N}"}
+    for var in (0, 4, 5):
+        outs = {}
+        for name, (kc, vc) in caches.items():
+            outs[name] = torch.empty_like(q)
+            ext.attn_prefill_paged(outs[name], q, cu_q, q_pos, kc, vc, bt, kvl,
+                                   scale, var)
+        torch.cuda.synchronize()
+        rec[f"v{var}_bit_equal"] = bool(torch.equal(outs["fp8"], outs["bf16"]))
+    for _ in range(2):
+        for var in (0, 4, 5):
+            for name, (kc, vc) in caches.items():
+                for _ in range(2):
+                    ext.attn_prefill_paged(out, q, cu_q, q_pos, kc, vc, bt, kvl,
+                                           scale, var)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    ext.attn_prefill_paged(out, q, cu_q, q_pos, kc, vc, bt, kvl,
+                                           scale, var)
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) / iters
+                rec.setdefault(f"TF_v{var}_{name}", []).append(
+                    round(flops / dt / 1e12, 1)
+                )
+    print(json.dumps(rec), flush=True)
+
+
 if __name__ == "__main__":
     for n in (2048, 4096, 8192):
-        probe(N=n)
+        if "--kv-fp8" in sys.argv:
+            probe_kv_fp8(N=n)
+        else:
+            probe(N=n)
