@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from dts_amd import ops
 from dts_amd.models.config import ModelSpec
 from dts_amd.serving.batch import ForwardBatch
+from dts_amd.serving.kv_cache import unpack_kv_layer
 
 
 class GPT2Layer(nn.Module):
@@ -54,8 +55,10 @@ class GPT2Layer(nn.Module):
         q = q.view(T, self.num_heads, self.head_dim)
         k = k.view(T, self.num_heads, self.head_dim)
         v = v.view(T, self.num_heads, self.head_dim)
-        k_cache, v_cache = kv_layer
-        ops.kv_append(k, v, k_cache, v_cache, batch.slot_mapping)
+        k_cache, v_cache, kv_scale, observe = unpack_kv_layer(kv_layer)
+        if observe is not None:
+            observe(k, v)
+        ops.kv_append(k, v, k_cache, v_cache, batch.slot_mapping, kv_scale)
 
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         np_tok = batch.num_prefill_tokens
@@ -64,12 +67,13 @@ class GPT2Layer(nn.Module):
                 q[:np_tok], batch.cu_q, batch.positions[:np_tok],
                 k_cache, v_cache, batch.prefill_block_tables,
                 batch.prefill_kv_lens, self.scale, out=out[:np_tok],
+                kv_scale=kv_scale,
             )
         if batch.num_decode_seqs:
             ops.attn_decode_paged(
                 q[np_tok:], k_cache, v_cache,
                 batch.decode_block_tables, batch.decode_kv_lens, self.scale,
-                out=out[np_tok:],
+                out=out[np_tok:], kv_scale=kv_scale,
             )
         hidden = hidden + F.linear(out.reshape(T, -1), self.o_w, self.o_b)
         x = ops.layernorm(hidden, self.ln2_w, self.ln2_b, self.eps)

@@ -32,6 +32,7 @@ from dts_amd.parallel.tp import (
     _init_weight,
 )
 from dts_amd.serving.batch import ForwardBatch
+from dts_amd.serving.kv_cache import unpack_kv_layer
 
 
 class LlamaAttention(nn.Module):
@@ -59,7 +60,7 @@ class LlamaAttention(nn.Module):
         self,
         hidden: torch.Tensor,  # [T, H]
         batch: ForwardBatch,
-        kv_layer: tuple,  # (k_cache, v_cache) for this layer
+        kv_layer: tuple,  # KVCachePool.layer(i), or a plain (k_cache, v_cache)
         rope: tuple,  # (cos, sin)
     ) -> torch.Tensor:
         T = hidden.shape[0]
@@ -69,11 +70,14 @@ class LlamaAttention(nn.Module):
         k = k.view(T, self.num_kv_heads, self.head_dim)
         v = v.view(T, self.num_kv_heads, self.head_dim)
 
-        k_cache, v_cache = kv_layer
+        k_cache, v_cache, kv_scale, observe = unpack_kv_layer(kv_layer)
         cos, sin = rope
         q, k = ops.rope_kv_append(
-            q, k, v, batch.positions, cos, sin, k_cache, v_cache, batch.slot_mapping
+            q, k, v, batch.positions, cos, sin, k_cache, v_cache,
+            batch.slot_mapping, kv_scale,
         )
+        if observe is not None:
+            observe(k, v)  # k after RoPE: what a bf16 cache would hold
 
         # q may be a strided view of qkv; output is always dense. The
         # kernels write straight into the dense slices (dim-0 slices of a
@@ -92,6 +96,7 @@ class LlamaAttention(nn.Module):
                 batch.prefill_kv_lens,
                 self.scale,
                 out=out[:np_tok],
+                kv_scale=kv_scale,
             )
         if batch.num_decode_seqs:
             ops.attn_decode_paged(
@@ -102,6 +107,7 @@ class LlamaAttention(nn.Module):
                 batch.decode_kv_lens,
                 self.scale,
                 out=out[np_tok:],
+                kv_scale=kv_scale,
             )
         return self.o_proj(out.reshape(T, -1))
 

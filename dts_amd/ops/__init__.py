@@ -89,8 +89,11 @@ def layernorm(x, weight, bias, eps=1e-5):
     return torch_ref.layernorm(x, weight, bias, eps)
 
 
-def rope_kv_append(q, k, v, positions, cos, sin, k_cache, v_cache, slot_mapping):
+def rope_kv_append(
+    q, k, v, positions, cos, sin, k_cache, v_cache, slot_mapping, kv_scale=None
+):
     """Fused: RoPE(q,k) in place + append (k,v) into the paged cache.
+    kv_scale: optional fp32 [2, Hkv] power-of-two scales of an FP8 cache.
 
     Returns (q, k) rotated. One kernel on GPU (saves two round trips over
     HBM for k); reference path composes the two torch ops.
@@ -98,25 +101,28 @@ def rope_kv_append(q, k, v, positions, cos, sin, k_cache, v_cache, slot_mapping)
     if _on_gpu(q):
         ext = _require_hip()
         if ext is not None:
-            ext.rope_kv_append(q, k, v, positions, cos, sin, k_cache, v_cache, slot_mapping)
+            ext.rope_kv_append(
+                q, k, v, positions, cos, sin, k_cache, v_cache, slot_mapping,
+                kv_scale,
+            )
             return q, k
     q, k = torch_ref.rope_apply(q, k, positions, cos, sin)
-    torch_ref.kv_append(k, v, k_cache, v_cache, slot_mapping)
+    torch_ref.kv_append(k, v, k_cache, v_cache, slot_mapping, kv_scale)
     return q, k
 
 
-def kv_append(k, v, k_cache, v_cache, slot_mapping):
+def kv_append(k, v, k_cache, v_cache, slot_mapping, kv_scale=None):
     if _on_gpu(k):
         ext = _require_hip()
         if ext is not None:
-            ext.kv_append(k, v, k_cache, v_cache, slot_mapping)
+            ext.kv_append(k, v, k_cache, v_cache, slot_mapping, kv_scale)
             return
-    torch_ref.kv_append(k, v, k_cache, v_cache, slot_mapping)
+    torch_ref.kv_append(k, v, k_cache, v_cache, slot_mapping, kv_scale)
 
 
 def attn_prefill_paged(
     q, cu_q, q_positions, k_cache, v_cache, block_tables, kv_lens, scale=None,
-    out=None,
+    out=None, kv_scale=None,
 ):
     if _on_gpu(q):
         ext = _require_hip()
@@ -128,10 +134,12 @@ def attn_prefill_paged(
             ext.attn_prefill_paged(
                 out, q, cu_q, q_positions, k_cache, v_cache, block_tables, kv_lens,
                 scale if scale is not None else 1.0 / math.sqrt(q.shape[-1]),
+                kv_scale=kv_scale,
             )
             return out
     ref = torch_ref.attn_prefill_paged(
-        q, cu_q, q_positions, k_cache, v_cache, block_tables, kv_lens, scale
+        q, cu_q, q_positions, k_cache, v_cache, block_tables, kv_lens, scale,
+        kv_scale,
     )
     if out is not None:
         out.copy_(ref)
@@ -139,7 +147,10 @@ def attn_prefill_paged(
     return ref
 
 
-def attn_decode_paged(q, k_cache, v_cache, block_tables, kv_lens, scale=None, out=None):
+def attn_decode_paged(
+    q, k_cache, v_cache, block_tables, kv_lens, scale=None, out=None,
+    kv_scale=None,
+):
     if _on_gpu(q):
         ext = _require_hip()
         if ext is not None:
@@ -150,9 +161,12 @@ def attn_decode_paged(q, k_cache, v_cache, block_tables, kv_lens, scale=None, ou
             ext.attn_decode_paged(
                 out, q, k_cache, v_cache, block_tables, kv_lens,
                 scale if scale is not None else 1.0 / math.sqrt(q.shape[-1]),
+                kv_scale,
             )
             return out
-    ref = torch_ref.attn_decode_paged(q, k_cache, v_cache, block_tables, kv_lens, scale)
+    ref = torch_ref.attn_decode_paged(
+        q, k_cache, v_cache, block_tables, kv_lens, scale, kv_scale
+    )
     if out is not None:
         out.copy_(ref)
         return out

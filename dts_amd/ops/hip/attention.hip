@@ -36,18 +36,27 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 // FP8 KV cache (opt-in). Every kernel below takes the cache element type as
 // its last template parameter KV: short = bf16 (the default, and the code
 // the bf16 instantiations compile is the code they always compiled), or
-// unsigned char = OCP e4m3fn codes with scale 1.0. Every finite e4m3 value
-// is a bf16 value, so the load-side conversions are exact and everything
-// after the load is the bf16 kernel's arithmetic.
+// unsigned char = OCP e4m3fn codes. Every finite e4m3 value is a bf16 value,
+// so the load-side conversions are exact and everything after the load is
+// the bf16 kernel's arithmetic.
+//
+// Scales (FP8 only): kv_scale is an optional device pointer to fp32
+// [2, Hkv] (row 0 = K, row 1 = V), null = 1.0 everywhere. Stored value =
+// code * scale[kvh]; the scales are powers of two, so code * scale is still
+// exactly a bf16 value. The kernels read the scale through the pointer (a
+// captured graph sees a stable address). Decode folds the K scale into the
+// softmax scale and applies the V scale once to the published partial o;
+// prefill hands the scale to the conversion instruction, so LDS holds the
+// dequantised bf16 tile.
 // ---------------------------------------------------------------------------
 
 // 8 e4m3 bytes (two dwords) -> 8 bf16, element order = byte order
-DEV bf16x8 kv_deq8(u32x2 w) {
+DEV bf16x8 kv_deq8(u32x2 w, float s) {
   union { bf16x2 p[4]; bf16x8 v; } c;
-  c.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], 1.0f, false);
-  c.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], 1.0f, true);
-  c.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], 1.0f, false);
-  c.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], 1.0f, true);
+  c.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], s, false);
+  c.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[0], s, true);
+  c.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], s, false);
+  c.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[1], s, true);
   return c.v;
 }
 
@@ -71,7 +80,8 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
                    const KV* __restrict__ vcache,
                    const int* __restrict__ block_tables, // [B, max_blocks]
                    const int* __restrict__ kv_lens,      // [B]
-                   int max_blocks, int Hkv, float scale, long q_tstride) {
+                   int max_blocks, int Hkv, float scale, long q_tstride,
+                   const float* __restrict__ kv_scale) {  // [2, Hkv] or null
   constexpr int BS = 16;
   constexpr int NWAVE = 4;
   constexpr int LPK = 4;            // lanes per key
@@ -127,6 +137,12 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
   }
 
   const int* bt = block_tables + (long)seq * max_blocks;
+
+  // FP8 scales: score = (q . code) * k_scale * scale — one uniform factor
+  float sscale = scale;
+  if constexpr (sizeof(KV) == 1) {
+    if (kv_scale) sscale *= kv_scale[kvh];
+  }
 
   for (int page = page_lo + wave; page < page_hi; page += NWAVE) {
     const long blk = bt[page];
@@ -195,7 +211,7 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
       partial[g] += __shfl_xor(partial[g], 2, 64);
       if (c == 0)
         s_scores[wave][g][key_of_lane] =
-            (key_of_lane < valid) ? partial[g] * scale : -1e30f;
+            (key_of_lane < valid) ? partial[g] * sscale : -1e30f;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -276,6 +292,11 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
   }
   __syncthreads();
 
+  // FP8 scales: o accumulated V codes; the V scale goes on once, here
+  float vscale = 1.f;
+  if constexpr (sizeof(KV) == 1) {
+    if (kv_scale) vscale = kv_scale[Hkv + kvh];
+  }
   const int tid = threadIdx.x;
   for (int gd = tid; gd < G * (D / 2); gd += blockDim.x) {
     const int g = gd / (D / 2);
@@ -296,8 +317,13 @@ attn_decode_kernel(float* __restrict__ ws_m,  // [B, Hkv, S, G]
       ws_l[ws_base + g] = l_star;
     }
     float* wo = ws_o + (ws_base + g) * D;
-    wo[d0] = acc0;
-    wo[d0 + 1] = acc1;
+    if constexpr (sizeof(KV) == 1) {
+      wo[d0] = acc0 * vscale;
+      wo[d0 + 1] = acc1 * vscale;
+    } else {
+      wo[d0] = acc0;
+      wo[d0 + 1] = acc1;
+    }
   }
 }  // (D/2 pairs: valid for D=64 too — s_o is [.][.][D])
 
@@ -642,7 +668,8 @@ attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
                        const KV* __restrict__ vcache,
                        const int* __restrict__ block_tables,
                        const int* __restrict__ kv_lens, int max_blocks,
-                       int Hkv, float scale, long q_tstride) {
+                       int Hkv, float scale, long q_tstride,
+                       const float* __restrict__ kv_scale) {  // [2,Hkv]/null
   constexpr int BS = 16;
   constexpr int KCHUNKS = D / 32;
   constexpr int CTILES = D / 16;
@@ -666,6 +693,15 @@ attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
 
   __shared__ short k_lds[KSTEP][LDK];
   __shared__ short v_lds[KSTEP][LDK];
+
+  // FP8 scales of this kv-head, handed to the converting tile load
+  float k_scale = 1.f, v_scale = 1.f;
+  if constexpr (sizeof(KV) == 1) {
+    if (kv_scale) {
+      k_scale = kv_scale[kvh];
+      v_scale = kv_scale[Hkv + kvh];
+    }
+  }
 
   // Q B-fragments (persistent; layout identical to v1's A-frag)
   short q_frag[KCHUNKS][8];
@@ -717,9 +753,9 @@ attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
           if constexpr (sizeof(KV) == 1) {
             // FP8: 8 B per tensor, converted to the same 16 B of bf16
             *(bf16x8*)(&k_lds[key][d0]) =
-                kv_deq8(*(const u32x2*)(kcache + off));
+                kv_deq8(*(const u32x2*)(kcache + off), k_scale);
             *(bf16x8*)(&v_lds[key][d0]) =
-                kv_deq8(*(const u32x2*)(vcache + off));
+                kv_deq8(*(const u32x2*)(vcache + off), v_scale);
           } else {
             *(bf16x8*)(&k_lds[key][d0]) = *(const bf16x8*)(kcache + off);
             *(bf16x8*)(&v_lds[key][d0]) = *(const bf16x8*)(vcache + off);
@@ -914,7 +950,8 @@ attn_prefill_kernel(short* __restrict__ out,      // [Tq, Hq, D]
                     const KV* __restrict__ vcache,
                     const int* __restrict__ block_tables,
                     const int* __restrict__ kv_lens, int max_blocks, int Hkv,
-                    float scale, long q_tstride) {
+                    float scale, long q_tstride,
+                    const float* __restrict__ kv_scale) {  // [2, Hkv] or null
   constexpr int BS = 16;
   constexpr int KSTEP = 32;
   constexpr int KCHUNKS = D / 32;     // mfma k-chunks per QK^T
@@ -939,6 +976,14 @@ attn_prefill_kernel(short* __restrict__ out,      // [Tq, Hq, D]
 
   __shared__ short k_lds[KSTEP][LDK];
   __shared__ short v_lds[KSTEP][LDK];
+  // FP8 scales of this kv-head, handed to the converting tile load
+  float k_scale = 1.f, v_scale = 1.f;
+  if constexpr (sizeof(KV) == 1) {
+    if (kv_scale) {
+      k_scale = kv_scale[kvh];
+      v_scale = kv_scale[Hkv + kvh];
+    }
+  }
   // element-column swizzle within a row (8-element blocks stay contiguous)
   auto swz_col = [](int key, int col) -> int {
     if constexpr (SWZ) return ((col & ~7) ^ ((key & 7) << 3)) | (col & 7);
@@ -1013,8 +1058,8 @@ attn_prefill_kernel(short* __restrict__ out,      // [Tq, Hq, D]
               vcache + ((blk * Hkv + kvh) * BS + koff) * (long)D + d0;
           if constexpr (sizeof(KV) == 1) {
             // FP8: 8 B per tensor, converted to the same 16 B of bf16
-            *(bf16x8*)(&k_lds[key][dst]) = kv_deq8(*(const u32x2*)kp);
-            *(bf16x8*)(&v_lds[key][dst]) = kv_deq8(*(const u32x2*)vp);
+            *(bf16x8*)(&k_lds[key][dst]) = kv_deq8(*(const u32x2*)kp, k_scale);
+            *(bf16x8*)(&v_lds[key][dst]) = kv_deq8(*(const u32x2*)vp, v_scale);
           } else {
             *(bf16x8*)(&k_lds[key][dst]) = *(const bf16x8*)kp;
             *(bf16x8*)(&v_lds[key][dst]) = *(const bf16x8*)vp;
@@ -1166,13 +1211,14 @@ attn_prefill_kernel(short* __restrict__ out,      // [Tq, Hq, D]
 void attn_decode_paged(torch::Tensor out, torch::Tensor q,
                        torch::Tensor kcache, torch::Tensor vcache,
                        torch::Tensor block_tables, torch::Tensor kv_lens,
-                       double scale) {
+                       double scale, c10::optional<torch::Tensor> kv_scale) {
   const int B = q.size(0), Hq = q.size(1), D = q.size(2);
   const int Hkv = kcache.size(1);
   const int G = Hq / Hkv;
   const int max_blocks = block_tables.size(1);
   TORCH_CHECK(kcache.size(2) == 16, "block_size must be 16");
   const bool fp8 = kv_cache_is_fp8(kcache, vcache);
+  const float* kv_scale_p = kv_scale_ptr(kv_scale, kcache, fp8);
   TORCH_CHECK(block_tables.scalar_type() == torch::kInt32);
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == D, "q heads must be dense");
   TORCH_CHECK(out.is_contiguous(), "out must be contiguous");
@@ -1226,7 +1272,7 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q,
                      (const kv*)vcache.data_ptr(),                           \
                      (const int*)block_tables.data_ptr(),                    \
                      (const int*)kv_lens.data_ptr(), max_blocks, Hkv,        \
-                     (float)scale, q_tstride)
+                     (float)scale, q_tstride, kv_scale_p)
 #define DECODE_CASE(g, d)                                                    \
   do {                                                                       \
     if (fp8) DECODE_LAUNCH(g, d, unsigned char);                             \
@@ -1250,7 +1296,8 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q,
 void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                         torch::Tensor q_pos, torch::Tensor kcache,
                         torch::Tensor vcache, torch::Tensor block_tables,
-                        torch::Tensor kv_lens, double scale, int64_t swz) {
+                        torch::Tensor kv_lens, double scale, int64_t swz,
+                        c10::optional<torch::Tensor> kv_scale) {
   // variant select via DTS_PREFILL_V: 0 -> v1 (KSTEP=32 LDS softmax),
   // 1 -> v1+XOR swizzle (-24..-30%), 2/3 -> v2 ablation (reg-staged +
   // transposed-V; SLOWER, profiles/prefill_v2_ablation_r2.md),
@@ -1271,6 +1318,7 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
   TORCH_CHECK(!fp8 || swz == 0 || swz == 4 || swz == 5,
               "prefill variant ", swz, " (DTS_PREFILL_V) does not support an "
               "FP8 KV cache; use 0, 4 or 5");
+  const float* kv_scale_p = kv_scale_ptr(kv_scale, kcache, fp8);
   const int Hq = q.size(1), D = q.size(2);
   const int Hkv = kcache.size(1);
   const int G = Hq / Hkv;
@@ -1324,7 +1372,7 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                          (const short*)vcache.data_ptr(),                     \
                          (const int*)block_tables.data_ptr(),                 \
                          (const int*)kv_lens.data_ptr(), max_blocks, Hkv,     \
-                         (float)scale, q_tstride);                            \
+                         (float)scale, q_tstride, nullptr);                   \
     else if (swz == 5)                                                        \
       hipLaunchKernelGGL((attn_prefill_kernel_v5<g, d, 64>), grid, block, 0,  \
                          stream, (short*)out.data_ptr(),                      \
@@ -1335,7 +1383,7 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                          (const short*)vcache.data_ptr(),                     \
                          (const int*)block_tables.data_ptr(),                 \
                          (const int*)kv_lens.data_ptr(), max_blocks, Hkv,     \
-                         (float)scale, q_tstride);                            \
+                         (float)scale, q_tstride, nullptr);                   \
     else if (swz == 1)                                                        \
       hipLaunchKernelGGL((attn_prefill_kernel<g, d, true>), grid, block, 0,   \
                          stream, (short*)out.data_ptr(),                      \
@@ -1346,7 +1394,7 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                          (const short*)vcache.data_ptr(),                     \
                          (const int*)block_tables.data_ptr(),                 \
                          (const int*)kv_lens.data_ptr(), max_blocks, Hkv,     \
-                         (float)scale, q_tstride);                            \
+                         (float)scale, q_tstride, nullptr);                   \
     else                                                                      \
       hipLaunchKernelGGL((attn_prefill_kernel<g, d, false>), grid, block, 0,  \
                          stream, (short*)out.data_ptr(),                      \
@@ -1357,7 +1405,7 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                          (const short*)vcache.data_ptr(),                     \
                          (const int*)block_tables.data_ptr(),                 \
                          (const int*)kv_lens.data_ptr(), max_blocks, Hkv,     \
-                         (float)scale, q_tstride);                            \
+                         (float)scale, q_tstride, nullptr);                   \
   } while (0)
 #define PREFILL_LAUNCH_FP8(kern)                                              \
   hipLaunchKernelGGL(kern, grid, block, 0, stream, (short*)out.data_ptr(),    \
@@ -1367,7 +1415,7 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                      (const unsigned char*)vcache.data_ptr(),                 \
                      (const int*)block_tables.data_ptr(),                     \
                      (const int*)kv_lens.data_ptr(), max_blocks, Hkv,         \
-                     (float)scale, q_tstride)
+                     (float)scale, q_tstride, kv_scale_p)
 #define PREFILL_CASE_FP8(g, d)                                                \
   do {                                                                        \
     if (swz == 4)                                                             \

@@ -10,17 +10,20 @@ void layernorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                     torch::Tensor positions, torch::Tensor cos_t,
                     torch::Tensor sin_t, torch::Tensor k_cache,
-                    torch::Tensor v_cache, torch::Tensor slots);
+                    torch::Tensor v_cache, torch::Tensor slots,
+                    c10::optional<torch::Tensor> kv_scale);
 void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
-               torch::Tensor v_cache, torch::Tensor slots);
+               torch::Tensor v_cache, torch::Tensor slots,
+               c10::optional<torch::Tensor> kv_scale);
 void attn_decode_paged(torch::Tensor out, torch::Tensor q,
                        torch::Tensor kcache, torch::Tensor vcache,
                        torch::Tensor block_tables, torch::Tensor kv_lens,
-                       double scale);
+                       double scale, c10::optional<torch::Tensor> kv_scale);
 void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                         torch::Tensor q_pos, torch::Tensor kcache,
                         torch::Tensor vcache, torch::Tensor block_tables,
-                        torch::Tensor kv_lens, double scale, int64_t swz);
+                        torch::Tensor kv_lens, double scale, int64_t swz,
+                        c10::optional<torch::Tensor> kv_scale);
 void top_p_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temps,
                   torch::Tensor top_ps, torch::Tensor seeds);
 void derive_seeds(torch::Tensor out, torch::Tensor bases,
@@ -51,17 +54,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm", &layernorm, "LayerNorm (bf16, GPT-2 path)");
   m.def("rope_kv_append", &rope_kv_append,
         "fused rotate-half RoPE + paged KV append (bf16 q/k/v; bf16 or FP8 "
-        "e4m3fn cache)");
+        "e4m3fn cache; kv_scale: optional fp32 [2, Hkv] power-of-two scales "
+        "of an FP8 cache, row 0 = K, row 1 = V)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("positions"),
+        py::arg("cos"), py::arg("sin"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("slots"),
+        py::arg("kv_scale") = py::none());
   m.def("kv_append", &kv_append,
-        "paged KV append without RoPE (bf16 k/v; bf16 or FP8 e4m3fn cache)");
+        "paged KV append without RoPE (bf16 k/v; bf16 or FP8 e4m3fn cache; "
+        "kv_scale as for rope_kv_append)",
+        py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("slots"), py::arg("kv_scale") = py::none());
   m.def("attn_decode_paged", &attn_decode_paged,
-        "paged GQA decode attention (bf16 q/out, bf16 or FP8 e4m3fn cache)");
+        "paged GQA decode attention (bf16 q/out, bf16 or FP8 e4m3fn cache; "
+        "kv_scale as for rope_kv_append)",
+        py::arg("out"), py::arg("q"), py::arg("kcache"), py::arg("vcache"),
+        py::arg("block_tables"), py::arg("kv_lens"), py::arg("scale"),
+        py::arg("kv_scale") = py::none());
   m.def("attn_prefill_paged", &attn_prefill_paged,
-        "paged causal prefill attention (bf16 MFMA; bf16 or FP8 e4m3fn cache)",
+        "paged causal prefill attention (bf16 MFMA; bf16 or FP8 e4m3fn cache; "
+        "kv_scale as for rope_kv_append)",
         py::arg("out"), py::arg("q"), py::arg("cu_q"), py::arg("q_pos"),
         py::arg("kcache"), py::arg("vcache"), py::arg("block_tables"),
         py::arg("kv_lens"),
-        py::arg("scale"), py::arg("swz") = -1);
+        py::arg("scale"), py::arg("swz") = -1,
+        py::arg("kv_scale") = py::none());
   m.def("top_p_sample", &top_p_sample,
         "fused temperature softmax + top-p sampling (sort-free)");
   m.def("derive_seeds", &derive_seeds,

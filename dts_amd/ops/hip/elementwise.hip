@@ -186,7 +186,8 @@ __global__ void silu_mul_kernel(short* __restrict__ out,
 //   k: [T, Hk, D] bf16 (rotated in place, then written to k_cache)
 //   v: [T, Hk, D] bf16 (written to v_cache)
 //   cos/sin: [P, D/2] fp32;  caches: [N, Hk, BS, D] bf16, or (KV =
-//   unsigned char) FP8 e4m3fn codes of the same values, scale 1.0
+//   unsigned char) FP8 e4m3fn codes of the same values divided by an
+//   optional power-of-two scale per (K|V, kv-head)
 //   slot_mapping: [T] int64 flat slot  (block = slot/BS, off = slot%BS)
 // One wave per (token, head); lane l owns dims {l, l+D/2} when D==128
 // (pairs 2 per lane via the rotate-half pairing), fp32 math.
@@ -199,7 +200,8 @@ __global__ void rope_kv_append_kernel(
     const float* __restrict__ sin_t, KV* __restrict__ k_cache,
     KV* __restrict__ v_cache, const long* __restrict__ slots, int T, int Hq,
     int Hk, int D, int BS, long cache_head_stride, long cache_block_stride,
-    int do_rope, long q_tstride, long k_tstride, long v_tstride) {
+    int do_rope, long q_tstride, long k_tstride, long v_tstride,
+    const float* __restrict__ kv_scale) {  // FP8 only: [2, Hk] or null
   // q/k/v may be row-strided VIEWS of a fused qkv projection (token-row
   // stride != H*D): all row addressing goes through *_tstride.
   // unit = one (token, head); heads 0..Hq-1 are q, Hq..Hq+Hk-1 are k,
@@ -243,11 +245,16 @@ __global__ void rope_kv_append_kernel(
       // bf16 cache would hold (k: the rotated value AFTER its bf16 round
       // above). The clamp is required: the conversion gives NaN above 464.
       // 4 dims per lane so the 4 codes go out as one 32-bit store.
+      // With scales the code is of x / scale[K|V][kvh]: the scale is a
+      // power of two, so its reciprocal and the product are exact in fp32
+      // (null = 1.0: x * 1.0f is x, the unscaled bytes).
+      float inv = 1.f;
+      if (kv_scale) inv = 1.f / kv_scale[(is_v ? Hk : 0) + kvh];
       for (int i = lane * 4; i < D; i += WAVE * 4) {
         int w0 = *(const int*)(src + i);
         int w1 = *(const int*)(src + i + 2);
-        auto sat = [](int u) {
-          return fminf(fmaxf(bf2f((short)(u & 0xffff)), -448.f), 448.f);
+        auto sat = [inv](int u) {
+          return fminf(fmaxf(bf2f((short)(u & 0xffff)) * inv, -448.f), 448.f);
         };
         float f0 = sat(w0), f1 = sat(w0 >> 16);
         float f2 = sat(w1), f3 = sat(w1 >> 16);
@@ -327,14 +334,17 @@ static inline void check_qkv_layout(const torch::Tensor& t) {
 void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                     torch::Tensor positions, torch::Tensor cos_t,
                     torch::Tensor sin_t, torch::Tensor k_cache,
-                    torch::Tensor v_cache, torch::Tensor slots) {
+                    torch::Tensor v_cache, torch::Tensor slots,
+                    c10::optional<torch::Tensor> kv_scale) {
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(cos_t.scalar_type() == torch::kFloat32);
   check_qkv_layout(q);
   check_qkv_layout(k);
   check_qkv_layout(v);
   const bool fp8 = kv_cache_is_fp8(k_cache, v_cache);
+  const float* kv_scale_p = kv_scale_ptr(kv_scale, k_cache, fp8);
   int T = q.size(0), Hq = q.size(1), D = q.size(2), Hk = k.size(1);
+  TORCH_CHECK(Hk == k_cache.size(1), "k heads must match the cache's");
   TORCH_CHECK(!fp8 || D % 4 == 0, "FP8 append needs head_dim % 4 == 0");
   int BS = k_cache.size(2);
   long head_stride = k_cache.stride(1), block_stride = k_cache.stride(0);
@@ -352,7 +362,7 @@ void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                      (kv*)k_cache.data_ptr(), (kv*)v_cache.data_ptr(),        \
                      (const long*)slots.data_ptr(), T, Hq, Hk, D, BS,         \
                      head_stride, block_stride, 1, q.stride(0), k.stride(0),  \
-                     v.stride(0))
+                     v.stride(0), kv_scale_p)
   if (fp8) ROPE_APPEND_LAUNCH(unsigned char);
   else ROPE_APPEND_LAUNCH(short);
 #undef ROPE_APPEND_LAUNCH
@@ -360,11 +370,14 @@ void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 }
 
 void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
-               torch::Tensor v_cache, torch::Tensor slots) {
+               torch::Tensor v_cache, torch::Tensor slots,
+               c10::optional<torch::Tensor> kv_scale) {
   // no-rope append (GPT-2 path): reuse the same kernel with Hq = 0 and a
   // null q/rope — implemented by passing k as q with Hq=0.
   const bool fp8 = kv_cache_is_fp8(k_cache, v_cache);
+  const float* kv_scale_p = kv_scale_ptr(kv_scale, k_cache, fp8);
   int T = k.size(0), Hk = k.size(1), D = k.size(2);
+  TORCH_CHECK(Hk == k_cache.size(1), "k heads must match the cache's");
   TORCH_CHECK(!fp8 || D % 4 == 0, "FP8 append needs head_dim % 4 == 0");
   int BS = k_cache.size(2);
   // positions unused for the copy path, but required by signature — pass
@@ -381,7 +394,7 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
                      (kv*)k_cache.data_ptr(), (kv*)v_cache.data_ptr(),        \
                      (const long*)slots.data_ptr(), T, 0, Hk, D, BS,          \
                      head_stride, block_stride, 0, 0, k.stride(0),            \
-                     v.stride(0))
+                     v.stride(0), kv_scale_p)
   if (fp8) KV_APPEND_LAUNCH(unsigned char);
   else KV_APPEND_LAUNCH(short);
 #undef KV_APPEND_LAUNCH

@@ -90,12 +90,29 @@ def rope_apply(
 FP8_E4M3_MAX = 448.0
 
 
-def quantize_kv_fp8(x: torch.Tensor) -> torch.Tensor:
-    """The FP8 KV cache's store: OCP float8_e4m3fn at scale 1.0, round to
-    nearest even, saturating at +-448 (+-inf included). The clamp is
-    required: the plain cast gives NaN above 464. NaN in is unspecified.
-    Dequantisation (`.float()` / `.to(bfloat16)`) is exact."""
-    return x.float().clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+def quantize_kv_fp8(
+    x: torch.Tensor, scale: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    """The FP8 KV cache's store: OCP float8_e4m3fn, round to nearest even,
+    saturating at +-448 (+-inf included). The clamp is required: the plain
+    cast gives NaN above 464. NaN in is unspecified.
+
+    `scale` (None = 1.0) broadcasts over x ([T, Hkv, D]; a per-head scale is
+    [Hkv, 1]); the code is of x / scale and the stored value is code *
+    scale. Scales are powers of two, so x * (1 / scale) is exact in fp32 and
+    dequantisation (`.float() * scale`) is exact, into bf16 as well."""
+    xf = x.float()
+    if scale is not None:
+        xf = xf * (1.0 / scale.float())
+    return xf.clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+
+
+def _head_scales(kv_scale: Optional[torch.Tensor]):
+    """[2, Hkv] -> (k_scale, v_scale), each [Hkv, 1] to broadcast over
+    [T, Hkv, D]; (None, None) for no scales."""
+    if kv_scale is None:
+        return None, None
+    return kv_scale[0].float().unsqueeze(-1), kv_scale[1].float().unsqueeze(-1)
 
 
 def kv_append(
@@ -104,17 +121,21 @@ def kv_append(
     k_cache: torch.Tensor,  # [num_blocks, Hkv, block_size, D]
     v_cache: torch.Tensor,
     slot_mapping: torch.Tensor,  # [T] flat slot = block_id*block_size + offset
+    kv_scale: Optional[torch.Tensor] = None,  # FP8 cache only: fp32 [2, Hkv]
 ) -> None:
+    if kv_scale is not None and k_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError("kv_scale needs an FP8 (float8_e4m3fn) KV cache")
     block_size = k_cache.shape[2]
     blocks = torch.div(slot_mapping, block_size, rounding_mode="floor")
     offs = slot_mapping - blocks * block_size
     if k_cache.dtype == torch.float8_e4m3fn:
         # codes are written through a byte view (indexed assignment of FP8
         # tensors is not available on every device)
-        k_cache.view(torch.uint8)[blocks, :, offs] = quantize_kv_fp8(k).view(
+        ks, vs = _head_scales(kv_scale)
+        k_cache.view(torch.uint8)[blocks, :, offs] = quantize_kv_fp8(k, ks).view(
             torch.uint8
         )
-        v_cache.view(torch.uint8)[blocks, :, offs] = quantize_kv_fp8(v).view(
+        v_cache.view(torch.uint8)[blocks, :, offs] = quantize_kv_fp8(v, vs).view(
             torch.uint8
         )
         return
@@ -127,14 +148,21 @@ def gather_kv(
     v_cache: torch.Tensor,
     block_table: torch.Tensor,  # [n_blocks_for_seq]
     kv_len: int,
+    kv_scale: Optional[torch.Tensor] = None,  # FP8 cache only: fp32 [2, Hkv]
 ):
-    """Contiguous [kv_len, Hkv, D] K/V for one sequence (reference only)."""
+    """Contiguous [kv_len, Hkv, D] K/V for one sequence (reference only).
+    With kv_scale the FP8 codes come back dequantised, as fp32."""
+    if kv_scale is not None and k_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError("kv_scale needs an FP8 (float8_e4m3fn) KV cache")
     bs = k_cache.shape[2]
     n_blocks = (kv_len + bs - 1) // bs
     k = k_cache[block_table[:n_blocks]]  # [n, Hkv, bs, D]
     v = v_cache[block_table[:n_blocks]]
     k = k.permute(0, 2, 1, 3).reshape(n_blocks * bs, k_cache.shape[1], -1)[:kv_len]
     v = v.permute(0, 2, 1, 3).reshape(n_blocks * bs, v_cache.shape[1], -1)[:kv_len]
+    if kv_scale is not None:
+        ks, vs = _head_scales(kv_scale)
+        k, v = k.float() * ks, v.float() * vs
     return k, v
 
 
@@ -176,6 +204,7 @@ def attn_prefill_paged(
     block_tables: torch.Tensor,  # [P, max_blocks]
     kv_lens: torch.Tensor,  # [P] total kv length per seq (incl. new tokens)
     scale: Optional[float] = None,
+    kv_scale: Optional[torch.Tensor] = None,  # FP8 cache only: fp32 [2, Hkv]
 ) -> torch.Tensor:
     """Chunked-prefill attention: each query attends to cached prefix + the
     causal part of its own chunk. KV must already be appended to the cache."""
@@ -186,7 +215,7 @@ def attn_prefill_paged(
     for i in range(P):
         s, e = int(cu_q[i]), int(cu_q[i + 1])
         kv_len = int(kv_lens[i])
-        k, v = gather_kv(k_cache, v_cache, block_tables[i], kv_len)
+        k, v = gather_kv(k_cache, v_cache, block_tables[i], kv_len, kv_scale)
         out[s:e] = _sdpa(q[s:e], k, v, scale, causal_offset=q_positions[s:e])
     return out
 
@@ -198,13 +227,14 @@ def attn_decode_paged(
     block_tables: torch.Tensor,  # [B, max_blocks]
     kv_lens: torch.Tensor,  # [B]
     scale: Optional[float] = None,
+    kv_scale: Optional[torch.Tensor] = None,  # FP8 cache only: fp32 [2, Hkv]
 ) -> torch.Tensor:
     D = q.shape[-1]
     scale = scale or 1.0 / math.sqrt(D)
     out = torch.empty_like(q)
     for i in range(q.shape[0]):
         kv_len = int(kv_lens[i])
-        k, v = gather_kv(k_cache, v_cache, block_tables[i], kv_len)
+        k, v = gather_kv(k_cache, v_cache, block_tables[i], kv_len, kv_scale)
         out[i : i + 1] = _sdpa(q[i : i + 1], k, v, scale)
     return out
 

@@ -233,6 +233,11 @@ def main() -> None:
                    help="paged KV cache dtype: auto = the model dtype, fp8 = "
                         "e4m3 at half the bytes (default: auto, or "
                         "DTS_KV_CACHE_DTYPE)")
+    p.add_argument("--kv-scales", default=None, metavar="calibrate|FILE",
+                   help="per-head power-of-two scales of the FP8 KV cache: "
+                        "calibrate = on the built-in token set at start-up, "
+                        "or a JSON file written by save_kv_scales (default: "
+                        "unit scales, or DTS_KV_SCALES)")
     args = p.parse_args()
 
     def factory() -> LLM:
@@ -248,6 +253,7 @@ def main() -> None:
             weights_path=args.weights,
             weight_quant=args.weight_quant,
             kv_cache_dtype=args.kv_cache_dtype,
+            kv_scales=args.kv_scales,
         )
         backend = LocalBackend.single(engine, name=args.model)
         return LLM(backend, default_model=args.model)

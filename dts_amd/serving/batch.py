@@ -34,6 +34,29 @@ class ForwardBatch:
     # prefill chunk that completed its prompt + every decode token)
     sample_indices: Optional[torch.Tensor] = None
 
+    @classmethod
+    def single_prefill(
+        cls, token_ids: list, block_table: list, block_size: int, start: int = 0
+    ) -> "ForwardBatch":
+        """One sequence's prefill chunk `token_ids` at positions start..,
+        written to and attending over the blocks of `block_table`; logits
+        for the chunk's last token."""
+        n = len(token_ids)
+        pos = torch.arange(start, start + n, dtype=torch.long)
+        table = torch.tensor(block_table, dtype=torch.long)
+        slots = table[pos // block_size] * block_size + pos % block_size
+        return cls(
+            token_ids=torch.tensor(token_ids, dtype=torch.long),
+            positions=pos,
+            slot_mapping=slots,
+            num_prefill_seqs=1,
+            num_prefill_tokens=n,
+            cu_q=torch.tensor([0, n], dtype=torch.int32),
+            prefill_block_tables=table.to(torch.int32).unsqueeze(0),
+            prefill_kv_lens=torch.tensor([start + n], dtype=torch.int32),
+            sample_indices=torch.tensor([n - 1], dtype=torch.long),
+        )
+
     @property
     def num_tokens(self) -> int:
         return int(self.token_ids.shape[0])

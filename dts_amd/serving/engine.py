@@ -29,7 +29,13 @@ from dts_amd.llm.errors import ContextLengthError
 from dts_amd.llm.types import Completion, Message, SamplingParams, Usage
 from dts_amd.models.config import ModelSpec, get_model_spec
 from dts_amd.serving import structured
-from dts_amd.serving.kv_cache import BlockManager, KVCachePool
+from dts_amd.serving.batch import ForwardBatch
+from dts_amd.serving.kv_cache import (
+    BlockManager,
+    KVCachePool,
+    pow2_ceil_scales,
+    scales_from_amax,
+)
 from dts_amd.serving.sampler import Sampler
 from dts_amd.serving.scheduler import Scheduler
 from dts_amd.serving.sequence import Sequence
@@ -70,6 +76,7 @@ class ServingEngine:
         weights_path: Optional[str] = None,
         weight_quant: Optional[str] = None,
         kv_cache_dtype: Optional[str] = None,
+        kv_scales: Optional[object] = None,
     ) -> None:
         self.spec: ModelSpec = get_model_spec(model_name)
         # opt-in weight-only quantisation (models/quant.py); the
@@ -82,9 +89,9 @@ class ServingEngine:
                 f"unknown weight_quant {weight_quant!r} (supported: 'fp8')"
             )
         self.weight_quant = weight_quant
-        # opt-in FP8 (e4m3, scale 1.0) paged KV cache: half the bytes per
-        # cached token, so twice the blocks for the same memory. None and
-        # "auto" keep the model dtype. Same precedence as weight_quant.
+        # opt-in FP8 (e4m3) paged KV cache: half the bytes per cached
+        # token, so twice the blocks for the same memory. None and "auto"
+        # keep the model dtype. Same precedence as weight_quant.
         if kv_cache_dtype is None:
             kv_cache_dtype = os.environ.get("DTS_KV_CACHE_DTYPE") or None
         if kv_cache_dtype == "auto":
@@ -95,6 +102,13 @@ class ServingEngine:
                 "(supported: 'auto', 'fp8')"
             )
         self.kv_cache_dtype = kv_cache_dtype
+        # static power-of-two scales of the FP8 cache: None (unit),
+        # "calibrate", a JSON path, or [L, 2, Hkv] / [L, 2] values. Same
+        # precedence; applied at the end of construction.
+        if kv_scales is None:
+            kv_scales = os.environ.get("DTS_KV_SCALES") or None
+        if kv_scales is not None and kv_cache_dtype != "fp8":
+            raise ValueError("kv_scales needs kv_cache_dtype='fp8'")
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         if dtype is None:
@@ -259,6 +273,134 @@ class ServingEngine:
         self.req_count = 0
         self.req_latency_sum = 0.0
         self.req_latency_max = 0.0
+
+        self._kv_scales_kind = "unit" if kv_cache_dtype == "fp8" else None
+        if kv_scales is not None:
+            if isinstance(kv_scales, str) and kv_scales == "calibrate":
+                self.calibrate_kv_scales(builtin_calibration_prompts(self.spec))
+            elif isinstance(kv_scales, (str, os.PathLike)):
+                self.load_kv_scales(kv_scales)
+            else:
+                self.set_kv_scales(kv_scales)
+
+    # ------------------------------------------------------------------
+    # FP8 KV-cache scales
+    # ------------------------------------------------------------------
+    @property
+    def kv_scales(self) -> Optional[torch.Tensor]:
+        """fp32 [layers, 2 (K, V), kv_heads] of an FP8 cache, else None."""
+        return self.kv_pool.scales
+
+    def _require_empty_kv_pool(self) -> None:
+        if self.kv_pool.scales is None:
+            raise ValueError("KV scales need kv_cache_dtype='fp8'")
+        # every executed batch writes K/V, and what it wrote stays
+        # allocated or content-cached; codes stored under the old scales
+        # would silently change value
+        if self.steps or self.chain_steps or self.scheduler.has_work():
+            raise RuntimeError(
+                "KV scales are frozen once a request has run: set or "
+                "calibrate them on a fresh engine"
+            )
+
+    def set_kv_scales(self, scales, _kind: str = "loaded") -> torch.Tensor:
+        """Set the scales from a tensor / nested list [L, 2, Hkv] or
+        [L, 2] (broadcast over heads). Values are rounded UP to the next
+        power of two and clamped to [2^-20, 2^20]; non-positive or
+        non-finite values raise ValueError. In place, only on an engine
+        that has not run a request yet."""
+        self._require_empty_kv_pool()
+        self.kv_pool.set_scales(pow2_ceil_scales(scales))
+        self._kv_scales_kind = _kind
+        return self.kv_pool.scales
+
+    @torch.inference_mode()
+    def calibrate_kv_scales(self, prompts: list, headroom: float = 2.0) -> torch.Tensor:
+        """Run the ordinary prefill forward over `prompts` (token lists or
+        strings), record amax per (layer, kv-head) of K after RoPE and of
+        V, and set scale = 2^ceil(log2(headroom * amax / 448)) (1.0 where
+        amax is 0). The forward writes a scratch cache of the model dtype,
+        so the observed values are those a bf16 cache would hold and the
+        engine's pool, block manager, prefix cache and scheduler are not
+        touched. Returns the scale tensor."""
+        self._require_empty_kv_pool()
+        if getattr(getattr(self.model, "tp", None), "size", 1) > 1:
+            raise NotImplementedError(
+                "calibrate_kv_scales drives the model directly and has no "
+                "tensor-parallel protocol; calibrate on one device and load "
+                "the saved scales"
+            )
+        toks_list = [
+            self.tokenizer.encode(p) if isinstance(p, str) else [int(t) for t in p]
+            for p in prompts
+        ]
+        toks_list = [t[: self.spec.max_position] for t in toks_list if t]
+        if not toks_list:
+            raise ValueError("calibration needs at least one non-empty prompt")
+        bs = self.kv_pool.block_size
+        n_blocks = (max(len(t) for t in toks_list) + bs - 1) // bs
+        scratch = KVCachePool(
+            self.kv_pool.k.shape[0],
+            self.kv_pool.k.shape[2],
+            self.kv_pool.k.shape[4],
+            n_blocks,
+            bs,
+            dtype=self.dtype,
+            device=self.device,
+        )
+        scratch.start_observing()
+        chunk = 2048
+        table = list(range(n_blocks))
+        for toks in toks_list:
+            for start in range(0, len(toks), chunk):
+                batch = ForwardBatch.single_prefill(
+                    toks[start : start + chunk], table, bs, start
+                )
+                if self.device != "cpu":
+                    batch = batch.to(self.device)
+                self.model.forward(batch, scratch)
+        amax = scratch.stop_observing()
+        scales = scales_from_amax(amax.cpu(), headroom)
+        self.kv_pool.set_scales(scales)
+        self._kv_scales_kind = "calibrated"
+        return self.kv_pool.scales
+
+    def save_kv_scales(self, path) -> None:
+        """Write the scales as JSON: model name, k_scale and v_scale as
+        [layers][kv_heads] nested lists."""
+        import json
+
+        if self.kv_pool.scales is None:
+            raise ValueError("KV scales need kv_cache_dtype='fp8'")
+        s = self.kv_pool.scales.cpu()
+        with open(path, "w") as f:
+            json.dump(
+                {
+                    "model": self.spec.name,
+                    "k_scale": s[:, 0].tolist(),
+                    "v_scale": s[:, 1].tolist(),
+                },
+                f,
+            )
+
+    def load_kv_scales(self, path) -> torch.Tensor:
+        import json
+
+        with open(path) as f:
+            d = json.load(f)
+        if d.get("model") not in (None, self.spec.name):
+            raise ValueError(
+                f"KV scales in {path} are for model {d.get('model')!r}, "
+                f"not {self.spec.name!r}"
+            )
+        scales = torch.stack(
+            [
+                torch.tensor(d["k_scale"], dtype=torch.float32),
+                torch.tensor(d["v_scale"], dtype=torch.float32),
+            ],
+            dim=1,
+        )
+        return self.set_kv_scales(scales, _kind="loaded")
 
     # ------------------------------------------------------------------
     def submit_tokens(
@@ -716,6 +858,7 @@ class ServingEngine:
             "graph_steps": self.graph_steps,
             "weight_quant": self.weight_quant,
             "kv_cache_dtype": self.kv_cache_dtype,
+            "kv_scales": self._kv_scales_kind,
             "tokens_sampled": self.tokens_sampled,
             "tokens_prefilled": self.tokens_prefilled,
             "native_scheduler": type(self.scheduler).__name__ == "NativeScheduler",
@@ -736,6 +879,16 @@ class ServingEngine:
             "t_sample_s": round(self.t_sample, 2),
             "t_post_s": round(self.t_post, 2),
         }
+
+
+def builtin_calibration_prompts(spec: ModelSpec, n: int = 4, length: int = 256) -> list:
+    """The deterministic token set of kv_scales="calibrate": n prompts of
+    `length` tokens drawn uniformly over the vocabulary with a seeded
+    generator (needs no tokenizer or corpus, so random-weight and benchmark
+    runs can use it; real deployments calibrate on their own prompts)."""
+    g = torch.Generator().manual_seed(0x5CA1E)
+    length = min(length, spec.max_position)
+    return torch.randint(0, spec.vocab_size, (n, length), generator=g).tolist()
 
 
 def build_model(spec: ModelSpec, dtype, device, tp=None):

@@ -20,6 +20,10 @@ Cache layout (per layer): K and V each [num_blocks, n_kv_heads,
 block_size, head_dim] — one (block, kv-head) is a contiguous
 [block_size, head_dim] tile (16x128 bf16 = 4 KiB), the unit the CDNA4
 decode-attention kernel streams through LDS.
+
+An FP8 (e4m3) pool also owns static power-of-two scales, fp32 [layers, 2
+(K, V), kv_heads]: a cached value is code * scale. Scales never change
+once a block holds data, so copy_block and the prefix cache ignore them.
 """
 
 from __future__ import annotations
@@ -31,6 +35,45 @@ from typing import Optional
 import torch
 
 DEFAULT_BLOCK_SIZE = 16
+
+FP8_E4M3_MAX = 448.0
+KV_SCALE_MIN_EXP = -20
+KV_SCALE_MAX_EXP = 20
+
+
+def pow2_ceil_scales(values: torch.Tensor) -> torch.Tensor:
+    """Round positive finite fp32 values UP to the next power of two,
+    clamped to [2^-20, 2^20] (a power of two maps to itself). frexp gives
+    the exponent exactly — no log2 rounding at the boundaries, the
+    construction quantize_fp8_rowwise uses for weights."""
+    v = torch.as_tensor(values, dtype=torch.float32)
+    if not bool(torch.isfinite(v).all()) or not bool((v > 0).all()):
+        raise ValueError("KV scales must be positive and finite")
+    mant, exp = torch.frexp(v)  # v = mant * 2^exp, mant in [0.5, 1)
+    exp = torch.where(mant == 0.5, exp - 1, exp)
+    exp = exp.clamp(KV_SCALE_MIN_EXP, KV_SCALE_MAX_EXP)
+    return torch.ldexp(torch.ones_like(v), exp)
+
+
+def scales_from_amax(amax: torch.Tensor, headroom: float = 2.0) -> torch.Tensor:
+    """scale = 2^ceil(log2(headroom * amax / 448)); amax = 0 gives 1.0."""
+    a = torch.as_tensor(amax, dtype=torch.float32)
+    target = a * (float(headroom) / FP8_E4M3_MAX)
+    ok = target > 0
+    scales = pow2_ceil_scales(torch.where(ok, target, torch.ones_like(target)))
+    return torch.where(ok, scales, torch.ones_like(scales))
+
+
+def unpack_kv_layer(kv_layer: tuple) -> tuple:
+    """(k_cache, v_cache, kv_scale, observe) from KVCachePool.layer(i) or
+    from a hand-built (k_cache, v_cache): the last two default to None."""
+    n = len(kv_layer)
+    return (
+        kv_layer[0],
+        kv_layer[1],
+        kv_layer[2] if n > 2 else None,
+        kv_layer[3] if n > 3 else None,
+    )
 
 
 def chain_hash(prev_hash: int, tokens: tuple) -> int:
@@ -146,9 +189,67 @@ class KVCachePool:
         shape = (num_layers, num_blocks, num_kv_heads, block_size, head_dim)
         self.k = torch.zeros(shape, dtype=dtype, device=device)
         self.v = torch.zeros(shape, dtype=dtype, device=device)
+        # FP8 pool only: static scales, ones until set. The tensor is
+        # allocated once and only ever updated in place, so the per-layer
+        # views handed to the kernels (and captured graphs) stay valid.
+        self.scales: Optional[torch.Tensor] = None
+        if dtype == torch.float8_e4m3fn:
+            self.scales = torch.ones(
+                (num_layers, 2, num_kv_heads), dtype=torch.float32, device=device
+            )
+        # calibration only: amax [layers, 2, kv_heads] of what is appended
+        self._observed: Optional[torch.Tensor] = None
 
     def layer(self, i: int) -> tuple:
+        """(k, v) of layer i; an FP8 pool adds its [2, kv_heads] scales,
+        and an observing pool the layer's amax recorder."""
+        if self._observed is not None:
+            scales = self.scales[i] if self.scales is not None else None
+            return self.k[i], self.v[i], scales, self._observer(i)
+        if self.scales is not None:
+            return self.k[i], self.v[i], self.scales[i]
         return self.k[i], self.v[i]
+
+    def set_scales(self, scales: torch.Tensor) -> None:
+        """In-place update with [layers, 2, kv_heads] (or [layers, 2],
+        broadcast over heads) powers of two. The caller guarantees that no
+        block holds data."""
+        if self.scales is None:
+            raise ValueError("KV scales need an FP8 KV cache")
+        s = torch.as_tensor(scales, dtype=torch.float32)
+        if s.dim() == 2:
+            s = s.unsqueeze(-1)
+        if s.dim() != 3 or s.shape[:2] != self.scales.shape[:2] or s.shape[2] not in (
+            1,
+            self.scales.shape[2],
+        ):
+            raise ValueError(
+                f"KV scales must be [layers, 2, kv_heads] = "
+                f"{list(self.scales.shape)} or [layers, 2]; got {list(s.shape)}"
+            )
+        self.scales.copy_(s.expand_as(self.scales))
+
+    # -- calibration observer -------------------------------------------
+    def start_observing(self) -> None:
+        self._observed = torch.zeros(
+            (self.k.shape[0], 2, self.k.shape[2]),
+            dtype=torch.float32,
+            device=self.k.device,
+        )
+
+    def stop_observing(self) -> torch.Tensor:
+        obs, self._observed = self._observed, None
+        return obs
+
+    def _observer(self, i: int):
+        rec = self._observed[i]
+
+        def observe(k: torch.Tensor, v: torch.Tensor) -> None:
+            # k, v: [T, kv_heads, D], the values a bf16 cache would hold
+            torch.maximum(rec[0], k.float().abs().amax(dim=(0, 2)), out=rec[0])
+            torch.maximum(rec[1], v.float().abs().amax(dim=(0, 2)), out=rec[1])
+
+        return observe
 
     def copy_block(self, src: int, dst: int) -> None:
         """COW copy for fork of a partial tail block."""

@@ -238,7 +238,9 @@ def kv_fp8_probes(ext):
     """Decode attention on an FP8 (e4m3) paged KV cache against the bf16
     kernel: the B x kv grid and the 8 cycled caches of kernel_probes, both
     dtypes in this process, alternating, three rounds each (median). TB/s
-    counts the K/V bytes each dtype really moves."""
+    counts the K/V bytes each dtype really moves. The scaled row is the FP8
+    kernel reading per-head power-of-two scales from device memory
+    (kv_scale) on the same codes; *_spread_us is max - min of the rounds."""
     dev = "cuda"
     bf16 = torch.bfloat16
     Hq, Hkv, D, BS = 32, 8, 128, 16
@@ -262,7 +264,11 @@ def kv_fp8_probes(ext):
             rec = {"probe": f"attn_decode_kv_fp8_B{B}_kv{kv}",
                    "kv_MB_bf16": round(elems * 2 / 1e6, 1),
                    "kv_MB_fp8": round(elems / 1e6, 1)}
-            t16, t8 = [], []
+            kv_scale = torch.tensor(
+                [[2.0 ** (h - 4) for h in range(Hkv)],
+                 [2.0 ** (3 - h) for h in range(Hkv)]],
+                dtype=torch.float32, device=dev)
+            t16, t8, t8s = [], [], []
             for _ in range(3):
                 t16.append(_time_us(
                     lambda i: ext.attn_decode_paged(
@@ -272,12 +278,19 @@ def kv_fp8_probes(ext):
                     lambda i: ext.attn_decode_paged(
                         out, q, k8[i], v8[i], bt, kvl, D**-0.5),
                     layers, reps=1))
+                t8s.append(_time_us(
+                    lambda i: ext.attn_decode_paged(
+                        out, q, k8[i], v8[i], bt, kvl, D**-0.5, kv_scale),
+                    layers, reps=1))
             a, b = sorted(t16)[1], sorted(t8)[1]
             rec["bf16_us"] = round(a, 1)
             rec["fp8_us"] = round(b, 1)
             rec["bf16_TBps"] = round(elems * 2 / a / 1e6, 2)
             rec["fp8_TBps"] = round(elems / b / 1e6, 2)
             rec["speedup"] = round(a / b, 3)
+            rec["fp8_scaled_us"] = round(sorted(t8s)[1], 1)
+            rec["fp8_spread_us"] = round(max(t8) - min(t8), 1)
+            rec["fp8_scaled_spread_us"] = round(max(t8s) - min(t8s), 1)
             print(json.dumps(rec), flush=True)
             del k16, v16, k8, v8
 
