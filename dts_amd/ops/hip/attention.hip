@@ -931,6 +931,404 @@ attn_prefill_kernel_v5(short* __restrict__ out,      // [Tq, Hq, D]
 }
 
 // ---------------------------------------------------------------------------
+// Prefill (MFMA) v6 — v5 with the V operand through the transposed LDS
+// read, and (PF) a register-staged prefetch of the next K/V tile
+//
+// The arithmetic is v5's per output row: the same KSTEP=64 tiles from key
+// 0, the same swapped QK^T MFMAs in kc order, the same softmax block, the
+// same P·V MFMA order (ct, then h) and the same epilogue. Only the way
+// bytes reach the MFMA operands differs, so the output is bit-identical
+// to v5 (tests/ops/test_prefill_v6_gpu.py).
+//
+// 1. P·V B operand. v5 gathers vb[i] = v_lds[kk0+i][dim] with 8 two-byte
+//    LDS reads and packing per MFMA. ds_read_b64_tr_b16 delivers, per
+//    16-lane group g = lane>>4, a 4-row x 16-column block column-major:
+//    lane 4q+p supplies &V[r0+q][16ct+4p], lane i receives column 16ct+i
+//    of rows r0..r0+3. With r0 = h*32 + 8g that is vb[0..3], with r0+4 it
+//    is vb[4..7]: two reads build the fragment from the row-major tile.
+//    The read needs EXEC all ones (it sits at loop level; the only early
+//    return and the loop bounds are workgroup-uniform), 8-byte-aligned
+//    addresses and every lane's address in bounds (the tile is always 64
+//    full rows, zero-filled past kv_len).
+//
+//    V image and banks. The read banks on (addr/4) % 64 per 32-lane half,
+//    8 bytes (2 dwords) per lane, so a half is conflict-free only if its
+//    32 lanes tile all 64 banks. A half holds groups g0 (rows r0+q) and
+//    g0+1 (rows r0+8+q). With a row stride of S dwords lane (g,q,p) sits
+//    on bank 8*S*(g&1) + S*q + 8ct + 2p. The 2p term fills an 8-dword
+//    window, so the eight (g,q) windows must start on the eight distinct
+//    multiples of 8: S*q must be 0 mod 8, hence S = 8k, and then the
+//    group term 8*S*(g&1) = 64k*(g&1) is 0 mod 64 — groups g and g+1
+//    always collide. No plain row stride is conflict-free (v5's D+8 is
+//    2-way as well: S = 68, bank 32g + 4q + 2p, q=0,p=2 meets q=1,p=0).
+//    So the padding has two levels: rows are LDV = D+16 elements
+//    (S = 72 or 40 dwords, S*q = {0,8,16,24} or {0,40,16,56} mod 64), and
+//    every group of 8 rows is followed by 128 bytes (32 dwords), which
+//    shifts the odd group onto the other half of the banks: the windows
+//    start at {0,8,16,24, 32,40,48,56} (D=128) and {0,40,16,56,
+//    32,8,48,24} (D=64) — each bank once. The +4-row read shifts all
+//    lanes alike. For one lane every read of an iteration differs by a
+//    compile-time constant, so one address register and offset:
+//    immediates serve all 4*CTILES reads. The ds_write_b128 tile store
+//    writes whole 16-byte-aligned rows as before. K keeps v5's image.
+//
+// 2. PF: after tile i is published, the global loads of tile i+1 go to
+//    registers (4 x 16 B per tensor per thread at D=128) and are written
+//    to LDS behind the barrier that ends tile i's reads. The thread's
+//    block-table entries are fetched one tile further ahead, so no load
+//    address waits on a table read. Loads are unconditional: a key at or
+//    past kv_len is clamped to key kv_len-1 for the table index and the
+//    address (so no entry of a page at or past ceil(kv_len/16) is read
+//    and no slot past kv_len is touched) and zero-filled at the LDS
+//    write. Nothing is issued past the last tile.
+// ---------------------------------------------------------------------------
+
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
+
+template <int G, int D, int KSTEP, typename KV = short, bool PF = false>
+__global__ void __launch_bounds__(256)
+attn_prefill_kernel_v6(short* __restrict__ out,      // [Tq, Hq, D]
+                       const short* __restrict__ q,  // [Tq, Hq, D]
+                       const int* __restrict__ cu_q, // [P+1]
+                       const long* __restrict__ q_pos, // [Tq]
+                       const KV* __restrict__ kcache,
+                       const KV* __restrict__ vcache,
+                       const int* __restrict__ block_tables,
+                       const int* __restrict__ kv_lens, int max_blocks,
+                       int Hkv, float scale, long q_tstride,
+                       const float* __restrict__ kv_scale) {  // [2,Hkv]/null
+  static_assert(KSTEP == 64, "v6 is built for 64-key tiles");
+  constexpr int BS = 16;
+  constexpr int KCHUNKS = D / 32;
+  constexpr int CTILES = D / 16;
+  constexpr int LDS_PAD = 8;
+  constexpr int LDK = D + LDS_PAD;
+  constexpr int LDV = D + 16;           // V row stride (elements)
+  constexpr int VGRP = 8 * LDV + 64;    // 8 V rows + 128 bytes
+  constexpr int ROWS = 64;
+  constexpr int NIT = KSTEP * D / (256 * 8);  // 16-B pieces per thread
+  constexpr int KEYS_PER_IT = 256 * 8 / D;
+  constexpr bool FP8 = sizeof(KV) == 1;
+  const int POS_PER_WG = ROWS / G;
+
+  const int seq = blockIdx.y;
+  const int kvh = blockIdx.z;
+  const int Hq = Hkv * G;
+  const int q_start = cu_q[seq];
+  const int q_len = cu_q[seq + 1] - q_start;
+  const int tile = blockIdx.x;
+  if (tile * POS_PER_WG >= q_len) return;
+
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int kv_len = kv_lens[seq];
+  const int* bt = block_tables + (long)seq * max_blocks;
+
+  __shared__ __attribute__((aligned(16))) short k_lds[KSTEP][LDK];
+  __shared__ __attribute__((aligned(16))) short v_lds[(KSTEP / 8) * VGRP];
+  auto v_off = [](int key, int col) -> int {
+    return (key >> 3) * VGRP + (key & 7) * LDV + col;
+  };
+
+  // FP8 scales of this kv-head, handed to the converting tile load
+  float k_scale = 1.f, v_scale = 1.f;
+  if constexpr (FP8) {
+    if (kv_scale) {
+      k_scale = kv_scale[kvh];
+      v_scale = kv_scale[Hkv + kvh];
+    }
+  }
+
+  // Q B-fragments (persistent; layout identical to v1's A-frag)
+  short q_frag[KCHUNKS][8];
+  {
+    const int r = lane & 15;
+    const int row_global = wave * 16 + r;
+    const int pos_local = tile * POS_PER_WG + row_global / G;
+    const int head = row_global % G;
+    const bool valid_row = pos_local < q_len;
+    const int tok = q_start + (valid_row ? pos_local : 0);
+    const short* qp = q + (long)tok * q_tstride + (long)(kvh * G + head) * D;
+#pragma unroll
+    for (int kc = 0; kc < KCHUNKS; ++kc) {
+      const int kbase = kc * 32 + (lane >> 4) * 8;
+      bf16x8 v8 = *(const bf16x8*)(qp + kbase);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        q_frag[kc][i] = valid_row ? v8[i] : (short)0;
+    }
+  }
+  // this lane's softmax q (col of the swapped score tile)
+  const int my_q = lane & 15;
+  const int my_row_global = wave * 16 + my_q;
+  const long my_pos_local = tile * POS_PER_WG + my_row_global / G;
+  const bool my_valid = my_pos_local < q_len;
+  const long my_abs_pos = my_valid ? q_pos[q_start + my_pos_local] : -1;
+
+  f32x4 o_acc[CTILES];
+#pragma unroll
+  for (int ct = 0; ct < CTILES; ++ct) o_acc[ct] = {0.f, 0.f, 0.f, 0.f};
+  float run_m = -1e30f, run_l = 0.f;  // for q = my_q (replicated x4 lanes)
+
+  const int last_local_pos = min(q_len, tile * POS_PER_WG + POS_PER_WG) - 1;
+  const long last_abs_pos = q_pos[q_start + last_local_pos];
+  const int kv_hi = min((long)kv_len, last_abs_pos + 1);
+
+  // this thread's pieces of a tile: keys ld_key + it*KEYS_PER_IT (each in
+  // a page of its own), 8 elements from ld_d0 — v5's assignment
+  const int ld_key = threadIdx.x * 8 / D;
+  const int ld_d0 = threadIdx.x * 8 % D;
+  // this lane's transposed-read address for h = 0, ct = 0, rows r0..r0+3
+  const short* v_rd =
+      &v_lds[v_off(8 * (lane >> 4) + ((lane >> 2) & 3), 4 * (lane & 3))];
+
+  using stage_t = typename std::conditional<FP8, u32x2, bf16x8>::type;
+  stage_t kreg[NIT], vreg[NIT];  // PF: the next tile, as loaded
+  int blk_next[NIT];             // PF: table entries of the tile to load
+  auto fetch_bt = [&](int base) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int kg = min(base + ld_key + it * KEYS_PER_IT, kv_len - 1);
+      blk_next[it] = bt[kg / BS];
+    }
+  };
+  auto issue_tile = [&](int base) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int kg = min(base + ld_key + it * KEYS_PER_IT, kv_len - 1);
+      const long off =
+          (((long)blk_next[it] * Hkv + kvh) * BS + kg % BS) * (long)D + ld_d0;
+      kreg[it] = *(const stage_t*)(kcache + off);
+      vreg[it] = *(const stage_t*)(vcache + off);
+    }
+  };
+  auto commit_tile = [&](int base) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int key = ld_key + it * KEYS_PER_IT;
+      const bool live = base + key < kv_len;
+      bf16x8 k8, v8;
+      if constexpr (FP8) {
+        k8 = kv_deq8(kreg[it], k_scale);
+        v8 = kv_deq8(vreg[it], v_scale);
+      } else {
+        k8 = kreg[it];
+        v8 = vreg[it];
+      }
+      const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+      *(bf16x8*)(&k_lds[key][ld_d0]) = live ? k8 : z;
+      *(bf16x8*)(&v_lds[v_off(key, ld_d0)]) = live ? v8 : z;
+    }
+  };
+
+  if constexpr (PF) {
+    if (kv_hi > 0) {
+      fetch_bt(0);
+      issue_tile(0);
+      if (KSTEP < kv_hi) fetch_bt(KSTEP);
+      commit_tile(0);
+      __syncthreads();
+    }
+  }
+
+  for (int kv_base = 0; kv_base < kv_hi; kv_base += KSTEP) {
+    if constexpr (PF) {
+      // tile kv_base is in LDS: start the next one, and the table
+      // entries of the one after it
+      if (kv_base + KSTEP < kv_hi) {
+        issue_tile(kv_base + KSTEP);
+        if (kv_base + 2 * KSTEP < kv_hi) fetch_bt(kv_base + 2 * KSTEP);
+      }
+    } else {
+      // ---- cooperative K/V tile load (shared by all 4 waves)
+      const int elems = KSTEP * D;
+      for (int base = threadIdx.x * 8; base < elems; base += 256 * 8) {
+        const int key = base / D;
+        const int d0 = base % D;
+        const int kglob = kv_base + key;
+        if (kglob < kv_len) {
+          const long blk = bt[kglob / BS];
+          const long off =
+              ((blk * Hkv + kvh) * BS + kglob % BS) * (long)D + d0;
+          if constexpr (sizeof(KV) == 1) {
+            // FP8: 8 B per tensor, converted to the same 16 B of bf16
+            *(bf16x8*)(&k_lds[key][d0]) =
+                kv_deq8(*(const u32x2*)(kcache + off), k_scale);
+            *(bf16x8*)(&v_lds[v_off(key, d0)]) =
+                kv_deq8(*(const u32x2*)(vcache + off), v_scale);
+          } else {
+            *(bf16x8*)(&k_lds[key][d0]) = *(const bf16x8*)(kcache + off);
+            *(bf16x8*)(&v_lds[v_off(key, d0)]) =
+                *(const bf16x8*)(vcache + off);
+          }
+        } else {
+          const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+          *(bf16x8*)(&k_lds[key][d0]) = z;
+          *(bf16x8*)(&v_lds[v_off(key, d0)]) = z;
+        }
+      }
+      __syncthreads();
+    }
+
+    // ---- swapped QK^T: C'[key, q] tiles, KSTEP/16 of them
+    constexpr int STILES = KSTEP / 16;
+    f32x4 sc[STILES];
+#pragma unroll
+    for (int st = 0; st < STILES; ++st) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kc = 0; kc < KCHUNKS; ++kc) {
+        // A-frag = K rows: row = st*16 + (lane&15), k-dim = d chunk
+        const int key = st * 16 + (lane & 15);
+        const int d0 = kc * 32 + (lane >> 4) * 8;
+        bf16x8 k8 = *(bf16x8*)(&k_lds[key][d0]);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            k8, *(bf16x8*)q_frag[kc], acc, 0, 0, 0);
+      }
+      sc[st] = acc;  // rows: key = st*16 + (lane>>4)*4 + i; col: my_q
+    }
+
+    // ---- in-register online softmax for column my_q (v5's, verbatim)
+    float p[STILES][4];
+    float tmax = -1e30f;
+#pragma unroll
+    for (int st = 0; st < STILES; ++st)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const long key_abs = kv_base + st * 16 + (lane >> 4) * 4 + i;
+        const bool ok =
+            my_valid && key_abs <= my_abs_pos && key_abs < (long)kv_len;
+        p[st][i] = ok ? sc[st][i] * scale : -1e30f;
+        tmax = fmaxf(tmax, p[st][i]);
+      }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(run_m, tmax);
+    float alpha;
+    float rowsum = 0.f;
+    if (m_new > -1e30f) {
+      alpha = (run_m > -1e30f) ? __expf(run_m - m_new) : 0.f;
+#pragma unroll
+      for (int st = 0; st < STILES; ++st)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          p[st][i] = (p[st][i] > -1e30f) ? __expf(p[st][i] - m_new) : 0.f;
+          rowsum += p[st][i];
+        }
+    } else {
+      alpha = 1.f;
+#pragma unroll
+      for (int st = 0; st < STILES; ++st)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) p[st][i] = 0.f;
+    }
+    rowsum += __shfl_xor(rowsum, 16, 64);
+    rowsum += __shfl_xor(rowsum, 32, 64);
+    run_l = run_l * alpha + rowsum;
+    run_m = m_new;
+
+    // ---- P' -> P·V A-fragments in registers (v5's, verbatim)
+    unsigned int ppack[STILES][2];
+#pragma unroll
+    for (int st = 0; st < STILES; ++st) {
+#pragma unroll
+      for (int hpair = 0; hpair < 2; ++hpair) {
+        const unsigned int lo =
+            (unsigned short)f2bf(p[st][hpair * 2]);
+        const unsigned int hi =
+            (unsigned short)f2bf(p[st][hpair * 2 + 1]);
+        ppack[st][hpair] = lo | (hi << 16);
+      }
+    }
+    constexpr int HCH = KSTEP / 32;
+    bf16x8 pa[HCH];
+#pragma unroll
+    for (int h = 0; h < HCH; ++h) {
+      const int kb = 8 * (lane >> 4);     // within the 32-key chunk
+      const int st_a = h * 2 + kb / 16;   // score tile holding kb..kb+3
+      const int ga = (kb % 16) / 4;       // lane-group that owns them
+      const int st_b = h * 2 + (kb + 4) / 16;
+      const int gb = ((kb + 4) % 16) / 4;
+      unsigned int paw[4];
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr) {
+        unsigned int va = 0, vb2 = 0;
+#pragma unroll
+        for (int st = 0; st < STILES; ++st) {
+          const unsigned int ta =
+              (unsigned int)__shfl((int)ppack[st][pr], (ga << 4) | my_q, 64);
+          const unsigned int tb =
+              (unsigned int)__shfl((int)ppack[st][pr], (gb << 4) | my_q, 64);
+          if (st == st_a) va = ta;
+          if (st == st_b) vb2 = tb;
+        }
+        paw[pr] = va;
+        paw[2 + pr] = vb2;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        pa[h][2 * j] = (short)(paw[j] & 0xffff);
+        pa[h][2 * j + 1] = (short)(paw[j] >> 16);
+      }
+    }
+    // rescale O by alpha of row q' = (lane>>4)*4+i (held by lane q')
+#pragma unroll
+    for (int ct = 0; ct < CTILES; ++ct) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float al = __shfl(alpha, (lane >> 4) * 4 + i, 64);
+        o_acc[ct][i] *= al;
+      }
+    }
+    // ---- P·V: B-frag = keys h*32 + 8*(lane>>4) .. +7 of column
+    // ct*16 + (lane&15), by two transposed reads (rows r0.., r0+4..)
+#pragma unroll
+    for (int ct = 0; ct < CTILES; ++ct) {
+#pragma unroll
+      for (int h = 0; h < HCH; ++h) {
+        const short* vp = v_rd + h * 4 * VGRP + ct * 16;
+        const i16x4 lo =
+            __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)vp);
+        const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_i16x4*)(vp + 4 * LDV));
+        const bf16x8 vb = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o_acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            pa[h], vb, o_acc[ct], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // everyone done reading this tile
+    if constexpr (PF) {
+      if (kv_base + KSTEP < kv_hi) {
+        commit_tile(kv_base + KSTEP);
+        __syncthreads();
+      }
+    }
+  }
+
+  // ---- epilogue: normalize + store (invl of row q' via shfl)
+  {
+#pragma unroll
+    for (int ct = 0; ct < CTILES; ++ct) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = (lane >> 4) * 4 + i;
+        const float l = __shfl(run_l, row, 64);
+        const float invl = (l > 0.f) ? 1.f / l : 0.f;
+        const int row_global = wave * 16 + row;
+        const int pos_local = tile * POS_PER_WG + row_global / G;
+        if (pos_local >= q_len) continue;
+        const int head = row_global % G;
+        const int tok = q_start + pos_local;
+        const int dim = ct * 16 + (lane & 15);
+        out[((long)tok * Hq + kvh * G + head) * D + dim] =
+            f2bf(o_acc[ct][i] * invl);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Prefill (MFMA) v1 — KSTEP=32 reference implementation
 // ---------------------------------------------------------------------------
 
@@ -1301,23 +1699,28 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
   // variant select via DTS_PREFILL_V: 0 -> v1 (KSTEP=32 LDS softmax),
   // 1 -> v1+XOR swizzle (-24..-30%), 2/3 -> v2 ablation (reg-staged +
   // transposed-V; SLOWER, profiles/prefill_v2_ablation_r2.md),
-  // 4/5 -> v5 swapped-QK^T in-register softmax (KSTEP 32/64).
-  // Default: v5 KSTEP=64 — measured 149/195/242 TF at N=2k/4k/8k vs
-  // v1's 140/182/220 (PMC-guided: v1 parked 43% of wave cycles on the
-  // softmax LDS round-trip fences).
+  // 4/5 -> v5 swapped-QK^T in-register softmax (KSTEP 32/64),
+  // 6/7 -> v6 = v5 KSTEP=64 bit for bit, V operand by transposed LDS
+  // reads: 6 with the next-tile prefetch, 7 without (ablation). The
+  // prefetch wins at every grid size measured, 8 to 4096 workgroups
+  // (profiles/prefill_v6.jsonl), so there is no dispatch between them.
+  // v5 KSTEP=64 measured 149/195/242 TF at N=2k/4k/8k vs v1's
+  // 140/182/220 (PMC-guided: v1 parked 43% of wave cycles on the
+  // softmax LDS round-trip fences). Default: v6.
   if (swz < 0) {
     static int env_v = [] {
       const char* e = getenv("DTS_PREFILL_V");
       return e ? atoi(e) : -1;
     }();
-    swz = (env_v >= 0) ? env_v : 5;
+    swz = (env_v >= 0) ? env_v : 6;
   }
-  // FP8 cache: v1 (0) and v5 (4/5) have a converting tile load; the
-  // ablation variants read bf16 only.
+  // FP8 cache: v1 (0), v5 (4/5) and v6 (6/7) have a converting tile
+  // load; the ablation variants read bf16 only.
   const bool fp8 = kv_cache_is_fp8(kcache, vcache);
-  TORCH_CHECK(!fp8 || swz == 0 || swz == 4 || swz == 5,
+  const bool v6 = swz == 6 || swz == 7;
+  TORCH_CHECK(!fp8 || swz == 0 || swz == 4 || swz == 5 || v6,
               "prefill variant ", swz, " (DTS_PREFILL_V) does not support an "
-              "FP8 KV cache; use 0, 4 or 5");
+              "FP8 KV cache; use 0, 4, 5, 6 or 7");
   const float* kv_scale_p = kv_scale_ptr(kv_scale, kcache, fp8);
   const int Hq = q.size(1), D = q.size(2);
   const int Hkv = kcache.size(1);
@@ -1338,9 +1741,23 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
   dim3 grid(max_tiles, P, Hkv);
   dim3 block(256);
   auto stream = c10::hip::getCurrentHIPStream();
+  const bool v6_pf = swz == 6;
+#define PREFILL_LAUNCH_BF16(kern)                                             \
+  hipLaunchKernelGGL(kern, grid, block, 0, stream, (short*)out.data_ptr(),    \
+                     (const short*)q.data_ptr(), (const int*)cu_q.data_ptr(), \
+                     (const long*)q_pos.data_ptr(),                           \
+                     (const short*)kcache.data_ptr(),                         \
+                     (const short*)vcache.data_ptr(),                         \
+                     (const int*)block_tables.data_ptr(),                     \
+                     (const int*)kv_lens.data_ptr(), max_blocks, Hkv,         \
+                     (float)scale, q_tstride, nullptr)
 #define PREFILL_CASE(g, d)                                                    \
   do {                                                                        \
-    if (swz == 2)                                                             \
+    if (v6 && v6_pf)                                                          \
+      PREFILL_LAUNCH_BF16((attn_prefill_kernel_v6<g, d, 64, short, true>));   \
+    else if (v6)                                                              \
+      PREFILL_LAUNCH_BF16((attn_prefill_kernel_v6<g, d, 64, short, false>));  \
+    else if (swz == 2)                                                        \
       hipLaunchKernelGGL((attn_prefill_kernel_v2<g, d, 64>), grid, block, 0,  \
                          stream, (short*)out.data_ptr(),                      \
                          (const short*)q.data_ptr(),                          \
@@ -1418,7 +1835,13 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
                      (float)scale, q_tstride, kv_scale_p)
 #define PREFILL_CASE_FP8(g, d)                                                \
   do {                                                                        \
-    if (swz == 4)                                                             \
+    if (v6 && v6_pf)                                                          \
+      PREFILL_LAUNCH_FP8(                                                     \
+          (attn_prefill_kernel_v6<g, d, 64, unsigned char, true>));           \
+    else if (v6)                                                              \
+      PREFILL_LAUNCH_FP8(                                                     \
+          (attn_prefill_kernel_v6<g, d, 64, unsigned char, false>));          \
+    else if (swz == 4)                                                        \
       PREFILL_LAUNCH_FP8((attn_prefill_kernel_v5<g, d, 32, unsigned char>));  \
     else if (swz == 5)                                                        \
       PREFILL_LAUNCH_FP8((attn_prefill_kernel_v5<g, d, 64, unsigned char>));  \
@@ -1441,5 +1864,6 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
 #undef PREFILL_CASE
 #undef PREFILL_CASE_FP8
 #undef PREFILL_LAUNCH_FP8
+#undef PREFILL_LAUNCH_BF16
   HIP_CHECK_LAST();
 }
