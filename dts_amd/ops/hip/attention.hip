@@ -1618,6 +1618,11 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q,
   const bool fp8 = kv_cache_is_fp8(kcache, vcache);
   const float* kv_scale_p = kv_scale_ptr(kv_scale, kcache, fp8);
   TORCH_CHECK(block_tables.scalar_type() == torch::kInt32);
+  TORCH_CHECK(kv_lens.scalar_type() == torch::kInt32 && kv_lens.dim() == 1 &&
+                  kv_lens.size(0) >= B && kv_lens.is_contiguous(),
+              "kv_lens must be contiguous int32 with one entry per sequence (",
+              B, "); got ",
+              kv_lens.scalar_type(), " ", kv_lens.sizes());
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == D, "q heads must be dense");
   TORCH_CHECK(out.is_contiguous(), "out must be contiguous");
   const long q_tstride = q.stride(0);
@@ -1733,6 +1738,21 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor cu_q,
   TORCH_CHECK(D == 128 || D == 64, "prefill kernel supports head_dim 64/128");
   TORCH_CHECK(kcache.size(2) == 16, "block_size must be 16");
   TORCH_CHECK(cu_q.scalar_type() == torch::kInt32);
+  TORCH_CHECK(kv_lens.scalar_type() == torch::kInt32 && kv_lens.dim() == 1 &&
+                  kv_lens.size(0) >= P && kv_lens.is_contiguous(),
+              "kv_lens must be contiguous int32 with one entry per sequence (",
+              P, "); got ",
+              kv_lens.scalar_type(), " ", kv_lens.sizes());
+  TORCH_CHECK(block_tables.scalar_type() == torch::kInt32 &&
+                  block_tables.dim() == 2 && block_tables.size(0) >= P &&
+                  block_tables.is_contiguous(),
+              "block_tables must be contiguous int32 [P, max_blocks]; got ",
+              block_tables.scalar_type(), " ", block_tables.sizes());
+  TORCH_CHECK(q_pos.scalar_type() == torch::kInt64 && q_pos.dim() == 1 &&
+                  q_pos.size(0) >= q.size(0) && q_pos.is_contiguous(),
+              "q_pos must be contiguous int64 with one entry per query (",
+              q.size(0), "); got ",
+              q_pos.scalar_type(), " ", q_pos.sizes());
   // worst-case tiles per seq: computed on host from q sizes is per-layer
   // overhead; use Tq (total) as bound and let tiles beyond q_len exit.
   const long Tq = q.size(0);

@@ -277,10 +277,32 @@ __global__ void rope_kv_append_kernel(
 
 static inline int grid_rows(int T) { return T < 2048 ? T : 2048; }
 
+// The norm kernels read x, out/residual and w through raw bf16 pointers
+// with x's [T, H] dense addressing: every operand has to be exactly that.
+static inline void check_norm_rows(const torch::Tensor& t,
+                                   const torch::Tensor& x, const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 && t.is_contiguous() &&
+                  t.sizes() == x.sizes() && t.device() == x.device(),
+              name, " must be contiguous bfloat16 of x's shape ", x.sizes(),
+              " on x's device; got ", t.scalar_type(), " ", t.sizes(),
+              " strides ", t.strides());
+}
+
+static inline void check_norm_vec(const torch::Tensor& t,
+                                  const torch::Tensor& x, const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 && t.is_contiguous() &&
+                  t.dim() == 1 && t.size(0) == x.size(-1) &&
+                  t.device() == x.device(),
+              name, " must be contiguous bfloat16 [H] = [", x.size(-1),
+              "] on x's device; got ", t.scalar_type(), " ", t.sizes());
+}
+
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
   int T = x.numel() / x.size(-1), H = x.size(-1);
   TORCH_CHECK(H % (256 * 8) == 0 || H % 8 == 0, "H must be multiple of 8");
+  check_norm_rows(out, x, "out");
+  check_norm_vec(w, x, "w");
   hipLaunchKernelGGL((rmsnorm_kernel<256>), dim3(grid_rows(T)), dim3(256), 0,
                      c10::hip::getCurrentHIPStream(),
                      (short*)out.data_ptr(), (const short*)x.data_ptr(),
@@ -292,6 +314,9 @@ void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
                        torch::Tensor w, double eps) {
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
   int T = x.numel() / x.size(-1), H = x.size(-1);
+  TORCH_CHECK(H % 8 == 0, "H must be multiple of 8");
+  check_norm_rows(residual, x, "residual");
+  check_norm_vec(w, x, "w");
   hipLaunchKernelGGL((fused_add_rmsnorm_kernel<256>), dim3(grid_rows(T)),
                      dim3(256), 0, c10::hip::getCurrentHIPStream(),
                      (short*)x.data_ptr(), (short*)residual.data_ptr(),
@@ -304,6 +329,9 @@ void layernorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
   int T = x.numel() / x.size(-1), H = x.size(-1);
   TORCH_CHECK(H % 8 == 0);
+  check_norm_rows(out, x, "out");
+  check_norm_vec(w, x, "w");
+  check_norm_vec(b, x, "b");
   hipLaunchKernelGGL((layernorm_kernel<256>), dim3(grid_rows(T)), dim3(256),
                      0, c10::hip::getCurrentHIPStream(),
                      (short*)out.data_ptr(), (const short*)x.data_ptr(),
@@ -331,6 +359,16 @@ static inline void check_qkv_layout(const torch::Tensor& t) {
               "expected [T,H,D] with dense heads; got strides ", t.strides());
 }
 
+// positions / slots: one int64 per token, read through a raw long pointer
+static inline void check_token_index(const torch::Tensor& t, int64_t T,
+                                     const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kInt64 && t.dim() == 1 &&
+                  t.size(0) >= T && t.is_contiguous(),
+              name, " must be contiguous int64 with one entry per token (", T,
+              "); got ",
+              t.scalar_type(), " ", t.sizes());
+}
+
 void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                     torch::Tensor positions, torch::Tensor cos_t,
                     torch::Tensor sin_t, torch::Tensor k_cache,
@@ -344,6 +382,8 @@ void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   const bool fp8 = kv_cache_is_fp8(k_cache, v_cache);
   const float* kv_scale_p = kv_scale_ptr(kv_scale, k_cache, fp8);
   int T = q.size(0), Hq = q.size(1), D = q.size(2), Hk = k.size(1);
+  check_token_index(positions, T, "positions");
+  check_token_index(slots, T, "slots");
   TORCH_CHECK(Hk == k_cache.size(1), "k heads must match the cache's");
   TORCH_CHECK(!fp8 || D % 4 == 0, "FP8 append needs head_dim % 4 == 0");
   int BS = k_cache.size(2);
@@ -374,9 +414,16 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
                c10::optional<torch::Tensor> kv_scale) {
   // no-rope append (GPT-2 path): reuse the same kernel with Hq = 0 and a
   // null q/rope — implemented by passing k as q with Hq=0.
+  TORCH_CHECK(k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16,
+              "k and v must be bfloat16; got ", k.scalar_type(), " and ",
+              v.scalar_type());
+  check_qkv_layout(k);
+  check_qkv_layout(v);
   const bool fp8 = kv_cache_is_fp8(k_cache, v_cache);
   const float* kv_scale_p = kv_scale_ptr(kv_scale, k_cache, fp8);
   int T = k.size(0), Hk = k.size(1), D = k.size(2);
+  check_token_index(slots, T, "slots");
   TORCH_CHECK(Hk == k_cache.size(1), "k heads must match the cache's");
   TORCH_CHECK(!fp8 || D % 4 == 0, "FP8 append needs head_dim % 4 == 0");
   int BS = k_cache.size(2);

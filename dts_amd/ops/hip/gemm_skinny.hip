@@ -237,6 +237,11 @@ void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(counts.scalar_type() == torch::kInt32 &&
               offsets.scalar_type() == torch::kInt32);
   const int K = x.size(1), E = w.size(0), N = w.size(1);
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16,
+              "expert weights must be bfloat16; got ", w.scalar_type());
+  TORCH_CHECK(w.dim() == 3 && w.size(2) == K,
+              "expert weights must be [E, N, K] with K=", K, "; got ",
+              w.sizes());
   TORCH_CHECK(K % (NWAVES * KSTEP * KUNROLL) == 0, "K must be /512");
   const int tiles = (N + 15) / 16;
   hipLaunchKernelGGL(moe_grouped_kernel, dim3(tiles, E), dim3(NWAVES * WAVE),
@@ -308,6 +313,8 @@ void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(out.stride(1) == 1);
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M >= 1 && M <= 16, "skinny path is for M<=16");
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16,
+              "weight must be bfloat16; got ", w.scalar_type());
   TORCH_CHECK(K % (NWAVES * KSTEP * KUNROLL) == 0, "K must be /512");
   TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N);
   TORCH_CHECK(tiles_per_wg == 0 || tiles_per_wg == 1 || tiles_per_wg == 2 ||
@@ -343,6 +350,8 @@ void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   const int I = N / 2;
   TORCH_CHECK(M >= 1 && M <= 16, "skinny path is for M<=16");
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16,
+              "weight must be bfloat16; got ", w.scalar_type());
   TORCH_CHECK(K % (NWAVES * KSTEP * KUNROLL) == 0, "K must be /512");
   TORCH_CHECK(N == 2 * I && I % 16 == 0, "fused SwiGLU needs I % 16 == 0");
   TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == I);

@@ -84,6 +84,10 @@ void gemv_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w) {
   TORCH_CHECK(x.stride(1) == 1, "x rows must be dense");
   TORCH_CHECK(out.stride(1) == 1);
   const int M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16,
+              "weight must be bfloat16; got ", w.scalar_type());
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == K, "weight must be [N, K] with K=",
+              K, "; got ", w.sizes());
   TORCH_CHECK(K % 512 == 0, "K must be a multiple of 512");
   TORCH_CHECK(M >= 1 && M <= 8, "gemv path is for M<=8");
   const int row_groups = (N + RPW - 1) / RPW;
