@@ -133,6 +133,8 @@ class LLM:
         max_tokens: Optional[int] = None,
         top_p: float = 0.95,
         seed: Optional[int] = None,
+        top_k: int = 0,
+        min_p: float = 0.0,
         **_ignored,
     ) -> Completion:
         """Complete a chat; with structured_output, retry until valid JSON.
@@ -145,6 +147,8 @@ class LLM:
         params = SamplingParams(
             temperature=temperature,
             top_p=top_p,
+            top_k=top_k,
+            min_p=min_p,
             max_tokens=max_tokens
             or (DEFAULT_JSON_MAX_TOKENS if structured_output else DEFAULT_MAX_TOKENS),
             seed=seed,
@@ -184,6 +188,8 @@ class LLM:
         max_tokens: Optional[int] = None,
         top_p: float = 0.95,
         seed: Optional[int] = None,
+        top_k: int = 0,
+        min_p: float = 0.0,
         **_ignored,
     ):
         """Async iterator of text deltas (ref client.py:205-272). Backends
@@ -191,6 +197,8 @@ class LLM:
         params = SamplingParams(
             temperature=temperature,
             top_p=top_p,
+            top_k=top_k,
+            min_p=min_p,
             max_tokens=max_tokens or DEFAULT_MAX_TOKENS,
             seed=seed,
         )

@@ -74,11 +74,20 @@ class SamplingParams:
     engine additionally needs explicit token budgets (the reference relies on
     the remote API's implicit limits — SURVEY.md §4.1.7) and seeds for
     reproducible tests.
+
+    top_k, top_p and min_p are all honoured, on the device, in the order
+    top-k -> top-p -> min-p: top_k keeps the k largest logits (ties with
+    the k-th included; 0 or >= vocabulary disables it), top_p is the
+    nucleus over the distribution renormalised to those survivors, and
+    min_p then keeps p_i >= min_p * p_max. temperature <= 0 is greedy and
+    ignores all three. Guided (structured) rows apply the same filters over
+    their allowed sub-vocabulary.
     """
 
     temperature: float = 0.7
     top_p: float = 0.95
     top_k: int = 0  # 0 = disabled
+    min_p: float = 0.0  # 0 = disabled; in [0, 1]
     max_tokens: int = 256
     stop: list = field(default_factory=list)  # stop strings
     seed: Optional[int] = None

@@ -210,7 +210,35 @@ def _sampler_workspace(S: int, device):
     return ws
 
 
-def top_p_sample(logits, temperatures, top_ps, generators=None, seeds=None, out=None):
+_sampler_filter_ws: dict = {}
+
+
+def _sampler_filter_workspace(S: int, device):
+    """Cached extra workspace of the gridded filtered sampler: the radix
+    select's per-row digit counts [S, 3, 2048] and the k-th logit [S]."""
+    key = (str(device), S)
+    ws = _sampler_filter_ws.get(key)
+    if ws is None:
+        ws = (
+            torch.zeros(S, 3, 2048, dtype=torch.int32, device=device),
+            torch.zeros(S, dtype=torch.float32, device=device),
+        )
+        _sampler_filter_ws[key] = ws
+    return ws
+
+
+def top_p_sample(
+    logits, temperatures, top_ps, generators=None, seeds=None, out=None,
+    top_ks=None, min_ps=None,
+):
+    """top_ks (int32 [S], 0 = disabled) / min_ps (fp32 [S], 0 = disabled):
+    optional top-k and min-p filters, applied top-k -> top-p -> min-p. With
+    both None the unfiltered kernels run, with the arguments they always
+    had."""
+    if top_ks is not None or min_ps is not None:
+        return _sample_filtered(
+            logits, temperatures, top_ps, generators, seeds, out, top_ks, min_ps
+        )
     if _on_gpu(logits):
         ext = _require_hip()
         if ext is not None and seeds is not None:
@@ -229,6 +257,36 @@ def top_p_sample(logits, temperatures, top_ps, generators=None, seeds=None, out=
                 ext.top_p_sample(out, logits, temperatures, top_ps, seeds)
             return out
     return torch_ref.top_p_sample(logits, temperatures, top_ps, generators)
+
+
+def _sample_filtered(
+    logits, temperatures, top_ps, generators, seeds, out, top_ks, min_ps
+):
+    S, V = logits.shape
+    if top_ks is None:
+        top_ks = torch.zeros(S, dtype=torch.int32, device=logits.device)
+    if min_ps is None:
+        min_ps = torch.zeros(S, dtype=torch.float32, device=logits.device)
+    if _on_gpu(logits):
+        ext = _require_hip()
+        if ext is not None and seeds is not None:
+            if out is None:
+                out = torch.empty(S, dtype=torch.long, device=logits.device)
+            # same v1 / v2 rule as the unfiltered sampler
+            if V >= 4096 and S <= 32 and os.environ.get("DTS_SAMPLER_V1") != "1":
+                ext.sample_filtered_v2(
+                    out, logits, temperatures, top_ps, top_ks, min_ps, seeds,
+                    *_sampler_workspace(S, logits.device),
+                    *_sampler_filter_workspace(S, logits.device),
+                )
+            else:
+                ext.sample_filtered(
+                    out, logits, temperatures, top_ps, top_ks, min_ps, seeds
+                )
+            return out
+    return torch_ref.top_p_sample(
+        logits, temperatures, top_ps, generators, top_ks, min_ps
+    )
 
 
 def derive_seeds(out, bases, positions):

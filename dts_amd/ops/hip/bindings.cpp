@@ -33,6 +33,17 @@ void top_p_sample_v2(torch::Tensor out, torch::Tensor logits,
                      torch::Tensor seeds, torch::Tensor ws_max,
                      torch::Tensor ws_bins, torch::Tensor ws_slice,
                      torch::Tensor ws_tau);
+void sample_filtered(torch::Tensor out, torch::Tensor logits,
+                     torch::Tensor temps, torch::Tensor top_ps,
+                     torch::Tensor top_ks, torch::Tensor min_ps,
+                     torch::Tensor seeds);
+void sample_filtered_v2(torch::Tensor out, torch::Tensor logits,
+                        torch::Tensor temps, torch::Tensor top_ps,
+                        torch::Tensor top_ks, torch::Tensor min_ps,
+                        torch::Tensor seeds, torch::Tensor ws_max,
+                        torch::Tensor ws_bins, torch::Tensor ws_slice,
+                        torch::Tensor ws_tau, torch::Tensor ws_cnt,
+                        torch::Tensor ws_xk);
 void gemv_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w);
 void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                       int64_t tiles_per_wg, int64_t unroll);
@@ -85,6 +96,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "stateless (seed, position) mix for chained decode");
   m.def("top_p_sample_v2", &top_p_sample_v2,
         "gridded top-p sampler (vocab sliced across workgroups)");
+  m.def("sample_filtered", &sample_filtered,
+        "top-k -> top-p -> min-p sampling, one workgroup per row");
+  m.def("sample_filtered_v2", &sample_filtered_v2,
+        "gridded top-k -> top-p -> min-p sampling (radix-select top-k)");
   m.def("gemv_bf16", &gemv_bf16,
         "skinny-batch (M<=8) bf16 weight-streaming GEMV");
   m.def("gemm_skinny_bf16", &gemm_skinny_bf16,

@@ -313,19 +313,74 @@ def moe_grouped_linear(
     return out
 
 
+def top_k_active(top_k: int, V: int) -> bool:
+    """top-k filters for 1 <= top_k < V; 0 and >= V disable it."""
+    return 1 <= top_k < V
+
+
+def filtered_probs(
+    row: torch.Tensor,  # [V] logits (fp32, or fp64 for a reference)
+    t: float,
+    top_p: float,
+    top_k: int,
+    min_p: float,
+) -> torch.Tensor:
+    """[V] probabilities of one sampled row (t > 0) after the filters, in
+    the order top-k -> top-p -> min-p, renormalised; dropped tokens are 0.
+
+    top-k keeps {i : x[i] >= k-th largest logit}: ties at the k-th are all
+    kept, so the set does not depend on index or walk order. top-p runs on
+    the distribution renormalised over those survivors (sorted descending,
+    kept while the exclusive cumulative mass < top_p, the first always).
+    min-p keeps p_i >= min_p * p_max; the ratio to the maximum is the same
+    before and after a renormalisation, so only its place after top-p
+    matters. The maximum survives all three."""
+    x = row if row.dtype == torch.float64 else row.float()
+    V = x.shape[0]
+    keep = torch.ones(V, dtype=torch.bool, device=x.device)
+    if top_k_active(top_k, V):
+        xk = torch.topk(x, top_k).values[-1]
+        keep = x >= xk
+    y = torch.where(keep, x / t, torch.full_like(x, float("-inf")))
+    probs = torch.softmax(y, dim=-1)
+    if top_p < 1.0:
+        sorted_probs, sorted_idx = torch.sort(probs, descending=True)
+        cum = torch.cumsum(sorted_probs, dim=-1)
+        mask = (cum - sorted_probs) < top_p
+        mask[0] = True
+        nucleus = torch.zeros(V, dtype=torch.bool, device=x.device)
+        nucleus[sorted_idx[mask]] = True
+        keep = keep & nucleus
+    if min_p > 0.0:
+        keep = keep & (probs >= min_p * probs.max())
+    kept = probs * keep
+    return kept / kept.sum()
+
+
 def top_p_sample(
     logits: torch.Tensor,  # [B, V] fp32
     temperatures: torch.Tensor,  # [B]
     top_ps: torch.Tensor,  # [B]
     generators: Optional[list] = None,
+    top_ks: Optional[torch.Tensor] = None,  # [B] int, 0 = disabled
+    min_ps: Optional[torch.Tensor] = None,  # [B] in [0, 1], 0 = disabled
 ) -> torch.Tensor:
-    """Temperature + nucleus sampling; temperature<=0 means greedy."""
+    """Temperature + top-k -> nucleus -> min-p sampling; temperature<=0
+    means greedy (lowest index among equal maxima) and ignores the filters.
+    A row with top-k disabled and min_p == 0 takes the unfiltered branch."""
     B, V = logits.shape
     out = torch.empty(B, dtype=torch.long, device=logits.device)
     for i in range(B):
         t = float(temperatures[i])
         if t <= 0.0:
             out[i] = int(torch.argmax(logits[i]))
+            continue
+        k = int(top_ks[i]) if top_ks is not None else 0
+        mp = float(min_ps[i]) if min_ps is not None else 0.0
+        if top_k_active(k, V) or mp > 0.0:
+            kept = filtered_probs(logits[i], t, float(top_ps[i]), k, mp)
+            gen = generators[i] if generators else None
+            out[i] = torch.multinomial(kept, 1, generator=gen)
             continue
         probs = torch.softmax(logits[i].float() / t, dim=-1)
         p = float(top_ps[i])

@@ -76,6 +76,8 @@ class ChainRunner:
             s = {
                 "temps": torch.zeros(B, dtype=torch.float32, device=dev),
                 "top_ps": torch.ones(B, dtype=torch.float32, device=dev),
+                "top_ks": torch.zeros(B, dtype=torch.int32, device=dev),
+                "min_ps": torch.zeros(B, dtype=torch.float32, device=dev),
                 "bases": torch.zeros(B, dtype=torch.long, device=dev),
                 "seeds": torch.zeros(B, dtype=torch.long, device=dev),
                 "toks": torch.zeros(B, dtype=torch.long, device=dev),
@@ -101,9 +103,13 @@ class ChainRunner:
         temps = torch.zeros(B, dtype=torch.float32)
         tops = torch.ones(B, dtype=torch.float32)
         bases = torch.zeros(B, dtype=torch.long)
+        top_ks = torch.zeros(B, dtype=torch.int32)
+        min_ps = torch.zeros(B, dtype=torch.float32)
         for i, s in enumerate(seqs):
             temps[i] = s.params.temperature
             tops[i] = s.params.top_p
+            top_ks[i] = int(s.params.top_k)
+            min_ps[i] = float(s.params.min_p)
             bases[i] = (
                 int(s.params.seed)
                 if s.params.seed is not None
@@ -112,9 +118,17 @@ class ChainRunner:
         sp["temps"].copy_(temps, non_blocking=True)
         sp["top_ps"].copy_(tops, non_blocking=True)
         sp["bases"].copy_(bases, non_blocking=True)
+        # top-k / min-p: the statics are filled (and the filtered sampler
+        # launched) only when some row sets one; the sampler runs outside
+        # the captured graph, so the default path keeps its launches
+        filtered = any(s.params.top_k > 0 or s.params.min_p > 0.0 for s in seqs)
+        if filtered:
+            sp["top_ks"].copy_(top_ks, non_blocking=True)
+            sp["min_ps"].copy_(min_ps, non_blocking=True)
         return {
             "entry": entry,
             "sp": sp,
+            "filtered": filtered,
             "B": B,
             "n": n,
             "pinned": self._pinned[B],
@@ -130,12 +144,18 @@ class ChainRunner:
         entry["graph"].replay()
         # seeds from CURRENT positions (drawn index = qpos + 1)
         ops.derive_seeds(sp["seeds"], sp["bases"], st["positions"])
+        filt = (
+            {"top_ks": sp["top_ks"], "min_ps": sp["min_ps"]}
+            if ctx["filtered"]
+            else {}
+        )
         ops.top_p_sample(
             entry["logits"],
             sp["temps"],
             sp["top_ps"],
             seeds=sp["seeds"],
             out=sp["toks"],
+            **filt,
         )
         # stream this step's tokens to pinned host memory + event
         ctx["pinned"][i].copy_(sp["toks"], non_blocking=True)

@@ -422,6 +422,15 @@ class ServingEngine:
                 f"prompt token id out of range [0, {self.spec.vocab_size}): "
                 f"min={lo} max={hi}"
             )
+        top_k, min_p = params.top_k, params.min_p
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+            raise ValueError(f"top_k must be an integer >= 0 (0 disables): {top_k!r}")
+        if (
+            isinstance(min_p, bool)
+            or not isinstance(min_p, (int, float))
+            or not 0.0 <= min_p <= 1.0  # NaN fails both comparisons
+        ):
+            raise ValueError(f"min_p must be in [0, 1] (0 disables): {min_p!r}")
         if guide is not None and hasattr(guide, "token_budget"):
             # a finite form defines its own output size; never let a
             # free-text phase budget truncate it mid-form

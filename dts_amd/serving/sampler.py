@@ -4,6 +4,11 @@ Builds per-step temperature/top-p tensors for the sampled rows, applies
 constrained-decoding masks (serving/structured.py guides), and dispatches
 to the top-p sampler (HIP kernel on GPU — sort-free threshold sampler —
 or the torch reference on CPU). Seeded per-sequence for reproducibility.
+
+top_k / min_p (SamplingParams) are honoured in the order top-k -> top-p ->
+min-p, for free and guided rows alike (guided rows: over the allowed
+sub-vocabulary). The top_ks / min_ps tensors are built only when some row
+of the call sets a filter; otherwise the sampler call is the unfiltered one.
 """
 
 from __future__ import annotations
@@ -13,13 +18,33 @@ from typing import Optional
 import torch
 
 from dts_amd import ops
+from dts_amd.ops import torch_ref
+
+
+def _filtered(seq) -> bool:
+    return seq.params.top_k > 0 or seq.params.min_p > 0.0
+
+
+def _filter_tensors(seqs: list, device) -> tuple:
+    """(top_ks int32, min_ps fp32) on `device`, or (None, None) when no
+    sequence sets a filter."""
+    if not any(_filtered(s) for s in seqs):
+        return None, None
+    top_ks = torch.tensor([int(s.params.top_k) for s in seqs], dtype=torch.int32)
+    min_ps = torch.tensor(
+        [float(s.params.min_p) for s in seqs], dtype=torch.float32
+    )
+    return top_ks.to(device, non_blocking=True), min_ps.to(
+        device, non_blocking=True
+    )
 
 
 class Sampler:
     def __init__(self, device: str = "cpu") -> None:
         self.device = device
         self._generators: dict = {}  # seq_id -> torch.Generator
-        # (temps, top_ps) device tensors cached per batch composition —
+        # (temps, top_ps, top_ks, min_ps) device tensors cached per batch
+        # composition (the last two None when no row sets a filter) —
         # stable across decode stretches; saves two H2D uploads per step
         self._param_cache: dict = {}
         # allowed-list -> padded device index tensor (guided rows)
@@ -95,12 +120,28 @@ class Sampler:
             ],
             dtype=torch.long,
         ).to(dev, non_blocking=True)
-        return ops.top_p_sample(sub.contiguous(), temps, tops, seeds=seeds)
+        # top-k / min-p over the allowed sub-vocabulary: the -1e30 pads can
+        # enter the top-k set when k exceeds the real entries, but sit far
+        # below y = -30 and are never drawn
+        top_ks, min_ps = _filter_tensors([s for _, s, _ in guided], dev)
+        if top_ks is None:
+            return ops.top_p_sample(sub.contiguous(), temps, tops, seeds=seeds)
+        return ops.top_p_sample(
+            sub.contiguous(), temps, tops, seeds=seeds, top_ks=top_ks,
+            min_ps=min_ps,
+        )
 
     def _pick_constrained(self, sub_cpu: torch.Tensor, seq, allowed: list) -> int:
         t = seq.params.temperature
         if t <= 0.0:
             return int(allowed[int(sub_cpu.argmax())])
+        if _filtered(seq):
+            kept = torch_ref.filtered_probs(
+                sub_cpu, t, seq.params.top_p, int(seq.params.top_k),
+                float(seq.params.min_p),
+            )
+            pick = torch.multinomial(kept, 1, generator=self._generator_for(seq))
+            return int(allowed[int(pick)])
         probs = torch.softmax(sub_cpu / t, dim=-1)
         p = seq.params.top_p
         if p < 1.0 and probs.numel() > 1:
@@ -163,19 +204,27 @@ class Sampler:
             if len(free_rows) == S
             else logits[torch.as_tensor(free_rows, device=logits.device)]
         )
-        key = tuple((s.params.temperature, s.params.top_p) for s in free_seqs)
+        key = tuple(
+            (s.params.temperature, s.params.top_p, s.params.top_k, s.params.min_p)
+            for s in free_seqs
+        )
         cached = self._param_cache.get(key)
         if cached is None:
-            temps = torch.tensor([t for t, _ in key], dtype=torch.float32)
-            top_ps = torch.tensor([p for _, p in key], dtype=torch.float32)
+            temps = torch.tensor([k[0] for k in key], dtype=torch.float32)
+            top_ps = torch.tensor([k[1] for k in key], dtype=torch.float32)
             if logits.is_cuda:
                 temps = temps.to(logits.device)
                 top_ps = top_ps.to(logits.device)
+            top_ks, min_ps = _filter_tensors(
+                free_seqs, logits.device if logits.is_cuda else "cpu"
+            )
             if len(self._param_cache) > 256:
                 self._param_cache.clear()
-            self._param_cache[key] = (temps, top_ps)
-            cached = (temps, top_ps)
-        temps, top_ps = cached
+            cached = (temps, top_ps, top_ks, min_ps)
+            self._param_cache[key] = cached
+        temps, top_ps, top_ks, min_ps = cached
+        # no row filtered: the call below is the unfiltered one, unchanged
+        filt = {} if top_ks is None else {"top_ks": top_ks, "min_ps": min_ps}
 
         if logits.is_cuda:
             import random as _random
@@ -203,6 +252,7 @@ class Sampler:
                 temps,
                 top_ps,
                 seeds=seeds,
+                **filt,
             )
             picks_gpu = (
                 self._constrained_gpu(logits, guided, positions) if guided else None
@@ -225,7 +275,9 @@ class Sampler:
                     g = torch.Generator(device="cpu")
                     g.manual_seed(ops.mix_seed(int(s.params.seed), p))
                     gens.append(g)
-            toks = ops.top_p_sample(free_logits.cpu(), temps, top_ps, generators=gens)
+            toks = ops.top_p_sample(
+                free_logits.cpu(), temps, top_ps, generators=gens, **filt
+            )
         for i, t in zip(free_rows, toks):
             out[i] = int(t)
         return out
