@@ -128,12 +128,16 @@ class LlamaMLP(nn.Module):
         # gather, so the per-rank weight is itself a [2*I_rank, K] gate_up
         gup = self.gate_up_proj
         assert gup.bias is None and not gup.gather_output
-        if gup.weight_q is not None:
-            act = ops.linear_swiglu_w8a16(
+        if gup.weight_q is None:
+            act = ops.linear_swiglu(x, gup.weight)
+        elif gup.weight_q.dtype == torch.uint8:  # MXFP4 codes
+            act = ops.linear_swiglu_w4a16(
                 x, gup.weight_q, gup.weight_scale, gup.weight
             )
         else:
-            act = ops.linear_swiglu(x, gup.weight)
+            act = ops.linear_swiglu_w8a16(
+                x, gup.weight_q, gup.weight_scale, gup.weight
+            )
         return self.down_proj(act)
 
 

@@ -467,3 +467,61 @@ def linear_swiglu_w8a16(
             ext.gemm_skinny_swiglu_w8_bf16(out, x, w_q, w_scale)
             return out
     return silu_mul(linear_w8a16(x, w_q, w_scale, w_deq))
+
+
+# ---------------------------------------------------------------------------
+# MXFP4 weight-only (W4A16) projections — opt-in, see dts_amd/models/quant.py
+# ---------------------------------------------------------------------------
+
+def linear_w4a16(
+    x: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, w_deq: torch.Tensor
+) -> torch.Tensor:
+    """y = x @ W^T for an MXFP4-quantised linear: w_q uint8 [N, K/2] e2m1
+    codes, w_scale uint8 [N, K/32] e8m0 block scales, and w_deq the SAME
+    matrix dequantised into the model dtype (exact: power-of-two scales).
+
+    Decode batches (the _w8_skinny conditions) stream the MXFP4 copy — a
+    quarter of the bytes — through the W4A16 skinny GEMM; everything else
+    (prefill through hipBLASLt, CPU) is linear_bf16 on w_deq."""
+    if _w8_skinny(x, w_q):
+        ext = _require_hip()
+        if ext is not None:
+            out = torch.empty(
+                (x.shape[0], w_q.shape[0]), dtype=x.dtype, device=x.device
+            )
+            ext.gemm_skinny_w4_bf16(out, x, w_q, w_scale)
+            return out
+    return linear_bf16(x, w_deq)
+
+
+# Largest M at which the fused SwiGLU epilogue replaces GEMM + silu_mul.
+# Measured on MXFP4 bytes (Llama-3-8B gate_up,
+# profiles/microbench_fp4_skinny.jsonl; fused against the best plain GEMM,
+# which is four tiles per workgroup at every M, plus the 2.2-2.4 us that
+# silu_mul adds in the same file; us): M=1 23.0 vs 21.5 + 2.2, M=4 25.0 vs
+# 23.2 + 2.3, M=8 27.9 vs 27.3 measured, M=16 35.3 vs 30.9 measured. The
+# fused kernel's fixed two tiles lose to the plain GEMM's four from M=8.
+# M = 5..7 is not measured and takes the two-kernel path.
+_W4_SWIGLU_MAX_M = 4
+
+
+def linear_swiglu_w4a16(
+    x: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, w_deq: torch.Tensor
+) -> torch.Tensor:
+    """silu_mul(linear_w4a16(...)) for an MXFP4 fused gate_up weight
+    [gate ; up] ([2I, K/2] codes); returns [M, I]. The fused epilogue is
+    bit-identical to the two-kernel path, so the threshold is a pure
+    performance choice."""
+    if (
+        _w8_skinny(x, w_q)
+        and x.shape[0] <= _W4_SWIGLU_MAX_M
+        and w_q.shape[0] % 2 == 0
+    ):
+        ext = _require_hip()
+        if ext is not None:
+            out = torch.empty(
+                (x.shape[0], w_q.shape[0] // 2), dtype=x.dtype, device=x.device
+            )
+            ext.gemm_skinny_swiglu_w4_bf16(out, x, w_q, w_scale)
+            return out
+    return silu_mul(linear_w4a16(x, w_q, w_scale, w_deq))

@@ -33,6 +33,7 @@ def build(verbose: bool = True) -> Path:
         str(HIP_DIR / "gemv.hip"),
         str(HIP_DIR / "gemm_skinny.hip"),
         str(HIP_DIR / "gemm_skinny_fp8.hip"),
+        str(HIP_DIR / "gemm_skinny_fp4.hip"),
     ]
     module = load(
         name="_dts_hip",

@@ -56,6 +56,11 @@ void gemm_skinny_w8_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w_q,
                          int64_t unroll);
 void gemm_skinny_swiglu_w8_bf16(torch::Tensor out, torch::Tensor x,
                                 torch::Tensor w_q, torch::Tensor scale);
+void gemm_skinny_w4_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w_q,
+                         torch::Tensor scale, int64_t tiles_per_wg,
+                         int64_t unroll);
+void gemm_skinny_swiglu_w4_bf16(torch::Tensor out, torch::Tensor x,
+                                torch::Tensor w_q, torch::Tensor scale);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
@@ -122,4 +127,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_skinny_swiglu_w8_bf16", &gemm_skinny_swiglu_w8_bf16,
         "W8A16 gate_up GEMM with fused SwiGLU epilogue: w_q = [Wg; Wu], "
         "gate rows scale by scale[n], up rows by scale[I+n]");
+  m.def("gemm_skinny_w4_bf16", &gemm_skinny_w4_bf16,
+        "W4A16 skinny-M (M<=16) GEMM: MXFP4 weights, e2m1 codes uint8 "
+        "[N,K/2] (element 2i in the low nibble) with e8m0 block scales uint8 "
+        "[N,K/32], bf16 x/out, fp32 accumulation; tiles_per_wg as for "
+        "gemm_skinny_bf16, unroll 4/8/16 (8 needs K % 1024 == 0, 16 needs "
+        "K % 2048 == 0); 0 = auto",
+        py::arg("out"), py::arg("x"), py::arg("w_q"), py::arg("scale"),
+        py::arg("tiles_per_wg") = 0, py::arg("unroll") = 0);
+  m.def("gemm_skinny_swiglu_w4_bf16", &gemm_skinny_swiglu_w4_bf16,
+        "W4A16 gate_up GEMM with fused SwiGLU epilogue: w_q = [Wg; Wu] "
+        "MXFP4 codes [2I,K/2], scale [2I,K/32]");
 }

@@ -256,6 +256,28 @@ def linear_w8a16(x: torch.Tensor, w_q: torch.Tensor, scale: torch.Tensor) -> tor
     return ((x.float() @ w_q.float().T) * scale.float()).to(x.dtype)
 
 
+# e2m1 magnitudes by the low three code bits; bit 3 is the sign
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def dequantize_mxfp4(w_q: torch.Tensor, scale: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """OCP MXFP4 -> dense [N, K]: w_q uint8 [N, K/2] holds element 2i in the
+    low nibble of byte i and 2i+1 in the high nibble; scale uint8 [N, K/32]
+    is e8m0, 2^(b-127), one per block of 32 along K."""
+    N, K = w_q.shape[0], w_q.shape[1] * 2
+    codes = torch.stack((w_q & 0xF, w_q >> 4), dim=-1).reshape(N, K).long()
+    grid = torch.tensor(E2M1_GRID, dtype=torch.float32, device=w_q.device)
+    val = grid[codes & 7] * (1.0 - 2.0 * (codes >> 3).float())
+    s = torch.ldexp(torch.ones((), device=w_q.device), scale.int() - 127)
+    return (val.view(N, K // 32, 32) * s[:, :, None]).view(N, K).to(dtype)
+
+
+def linear_w4a16(x: torch.Tensor, w_q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """Numerics oracle of the W4A16 GEMM: fp32 product with the dequantised
+    MXFP4 matrix, one rounding to x.dtype."""
+    return (x.float() @ dequantize_mxfp4(w_q, scale).T).to(x.dtype)
+
+
 def gelu(x: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.gelu(x.float(), approximate="tanh").to(x.dtype)
 

@@ -60,8 +60,9 @@ def _init_weight(out_f: int, in_f: int, dtype, generator=None, device="cpu") -> 
 
 
 def _init_weight_quant(lin: nn.Module) -> None:
-    """Empty slots for the opt-in FP8 copy of the weight (weight_q [N, K]
-    e4m3fn + weight_scale [N] fp32), filled by models/quant.py. While they
+    """Empty slots for the opt-in quantised copy of the weight, filled by
+    models/quant.py: FP8 (weight_q [N, K] e4m3fn + weight_scale [N] fp32) or
+    MXFP4 (weight_q [N, K/2] uint8 + weight_scale [N, K/32] uint8). While they
     are None the layer is the plain bf16 linear."""
     lin.register_buffer("weight_q", None, persistent=False)
     lin.register_buffer("weight_scale", None, persistent=False)
@@ -90,10 +91,12 @@ class ColumnParallelLinear(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from dts_amd import ops
 
-        if self.weight_q is not None:
-            y = ops.linear_w8a16(x, self.weight_q, self.weight_scale, self.weight)
-        else:
+        if self.weight_q is None:
             y = ops.linear_bf16(x, self.weight)
+        elif self.weight_q.dtype == torch.uint8:  # MXFP4 codes
+            y = ops.linear_w4a16(x, self.weight_q, self.weight_scale, self.weight)
+        else:
+            y = ops.linear_w8a16(x, self.weight_q, self.weight_scale, self.weight)
         if self.bias is not None:
             y = y + self.bias
         if self.gather_output:
@@ -123,10 +126,12 @@ class RowParallelLinear(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from dts_amd import ops
 
-        if self.weight_q is not None:
-            y = ops.linear_w8a16(x, self.weight_q, self.weight_scale, self.weight)
-        else:
+        if self.weight_q is None:
             y = ops.linear_bf16(x, self.weight)
+        elif self.weight_q.dtype == torch.uint8:  # MXFP4 codes
+            y = ops.linear_w4a16(x, self.weight_q, self.weight_scale, self.weight)
+        else:
+            y = ops.linear_w8a16(x, self.weight_q, self.weight_scale, self.weight)
         y = self.tp.all_reduce(y)
         if self.bias is not None:
             y = y + self.bias

@@ -226,7 +226,7 @@ def main() -> None:
                    help="local HF tokenizers JSON (default: synthetic)")
     p.add_argument("--weights", default=None,
                    help="HF-layout safetensors dir (default: random-init)")
-    p.add_argument("--weight-quant", default=None, choices=["fp8"],
+    p.add_argument("--weight-quant", default=None, choices=["fp8", "mxfp4"],
                    help="weight-only quantisation of the Llama projections "
                         "(default: none, or DTS_WEIGHT_QUANT)")
     p.add_argument("--kv-cache-dtype", default=None, choices=["auto", "fp8"],

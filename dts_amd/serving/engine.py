@@ -84,9 +84,10 @@ class ServingEngine:
         # keyword (the benchmark)
         if weight_quant is None:
             weight_quant = os.environ.get("DTS_WEIGHT_QUANT") or None
-        if weight_quant not in (None, "fp8"):
+        if weight_quant not in (None, "fp8", "mxfp4"):
             raise ValueError(
-                f"unknown weight_quant {weight_quant!r} (supported: 'fp8')"
+                f"unknown weight_quant {weight_quant!r} "
+                "(supported: 'fp8', 'mxfp4')"
             )
         self.weight_quant = weight_quant
         # opt-in FP8 (e4m3) paged KV cache: half the bytes per cached
@@ -141,7 +142,7 @@ class ServingEngine:
             else:
                 self.model.random_init(seed=weight_seed)
         # after load/init and BEFORE the KV pool is sized from free memory:
-        # the FP8 copies are extra weight bytes the pool must leave room for
+        # the quantised copies are extra weight bytes the pool must leave room for
         if weight_quant is not None and (
             getattr(self.model, "weight_quant", None) != weight_quant
         ):

@@ -234,6 +234,84 @@ def fp8_kernel_probes(ext):
         del ws, ws16
 
 
+def fp4_kernel_probes(ext):
+    """W4A16 (MXFP4) skinny GEMM on the five Llama-3-8B shapes next to the
+    W8A16 and bf16 kernels' auto dispatch: the three dtypes alternate in this
+    process, three rounds each; every figure is the median round and
+    *_spread_us is max - min. The MXFP4 kernel is swept over
+    tiles-per-workgroup x unroll, plus its auto dispatch and, on gate_up,
+    the fused SwiGLU against GEMM + silu_mul. TB/s counts the weight bytes
+    each dtype really moves (codes + block scales for MXFP4). Weights cycle
+    through enough copies to exceed the 256 MB Infinity Cache."""
+    dev = "cuda"
+    bf16 = torch.bfloat16
+    shapes = (
+        ("qkv", 4096, 6144),
+        ("o", 4096, 4096),
+        ("gate_up", 4096, 28672),
+        ("down", 14336, 4096),
+        ("lm_head", 4096, 128256),
+    )
+    rounds = 3
+
+    def med(ts):
+        return round(sorted(ts)[len(ts) // 2], 1), round(max(ts) - min(ts), 1)
+
+    for name, K, N in shapes:
+        w4_bytes = N * K // 2 + N * K // 32
+        c4 = max(2, min(64, (512 << 20) // w4_bytes + 1))
+        c8 = max(2, min(32, (512 << 20) // (N * K) + 1))
+        c16 = max(2, min(8, (1 << 30) // (N * K * 2) + 1))
+        ws4 = [torch.randint(0, 256, (N, K // 2), dtype=torch.uint8, device=dev)
+               for _ in range(c4)]
+        sc4 = torch.randint(117, 123, (N, K // 32), dtype=torch.uint8, device=dev)
+        ws8 = []
+        for _ in range(c8):  # finite e4m3 codes
+            c = torch.randint(0, 127, (N, K), dtype=torch.uint8, device=dev)
+            ws8.append(c.view(torch.float8_e4m3fn))
+        del c
+        sc8 = torch.rand(N, device=dev) + 0.5
+        ws16 = [torch.randn(N, K, dtype=bf16, device=dev) for _ in range(c16)]
+        for M in (1, 4, 8, 16):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            out = torch.empty(M, N, dtype=bf16, device=dev)
+            act = torch.empty(M, N // 2, dtype=bf16, device=dev)
+            kus = [u for u in (4, 8, 16) if K % (128 * u) == 0]
+            fns = {
+                "bf16_auto": (lambda i: ext.gemm_skinny_bf16(out, x, ws16[i]), c16),
+                "fp8_auto": (lambda i: ext.gemm_skinny_w8_bf16(out, x, ws8[i], sc8), c8),
+                "auto": (lambda i: ext.gemm_skinny_w4_bf16(out, x, ws4[i], sc4), c4),
+            }
+            for nt in (1, 2, 4):
+                for ku in kus:
+                    fns[f"nt{nt}_ku{ku}"] = (
+                        lambda i, nt=nt, ku=ku: ext.gemm_skinny_w4_bf16(
+                            out, x, ws4[i], sc4, tiles_per_wg=nt, unroll=ku), c4)
+            if name == "gate_up":
+                def two_kernels(i):
+                    ext.gemm_skinny_w4_bf16(out, x, ws4[i], sc4)
+                    ext.silu_mul(act, out)
+
+                fns["gemm_auto_plus_silu_mul"] = (two_kernels, c4)
+                fns["fused_swiglu"] = (
+                    lambda i: ext.gemm_skinny_swiglu_w4_bf16(act, x, ws4[i], sc4), c4)
+            ts = {k: [] for k in fns}
+            for _ in range(rounds):
+                for k, (fn, copies) in fns.items():
+                    ts[k].append(_time_us(fn, copies, reps=1))
+            rec = {"probe": f"skinny_w4_{name}_M{M}_K{K}_N{N}", "copies": c4}
+            for k in fns:
+                rec[f"{k}_us"], rec[f"{k}_spread_us"] = med(ts[k])
+            rec["bf16_auto_TBps"] = round(N * K * 2 / rec["bf16_auto_us"] / 1e6, 2)
+            rec["fp8_auto_TBps"] = round(N * K / rec["fp8_auto_us"] / 1e6, 2)
+            rec["auto_TBps"] = round(w4_bytes / rec["auto_us"] / 1e6, 2)
+            pinned = {k: rec[f"{k}_us"] for k in fns if k.startswith("nt")}
+            rec["best_pinned"] = min(pinned, key=pinned.get)
+            rec["best_pinned_us"] = pinned[rec["best_pinned"]]
+            print(json.dumps(rec), flush=True)
+        del ws4, ws8, ws16
+
+
 def kv_fp8_probes(ext):
     """Decode attention on an FP8 (e4m3) paged KV cache against the bf16
     kernel: the B x kv grid and the 8 cycled caches of kernel_probes, both
@@ -300,6 +378,11 @@ def main():
         from dts_amd.ops import _hip_ext_loader
 
         kv_fp8_probes(_hip_ext_loader.load())
+        return
+    if "--fp4-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        fp4_kernel_probes(_hip_ext_loader.load())
         return
     if "--fp8-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
