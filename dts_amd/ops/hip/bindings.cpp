@@ -46,9 +46,11 @@ void sample_filtered_v2(torch::Tensor out, torch::Tensor logits,
                         torch::Tensor ws_xk);
 void gemv_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w);
 void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                      int64_t tiles_per_wg, int64_t unroll);
+                      int64_t tiles_per_wg, int64_t unroll,
+                      int64_t persistent);
 void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
-                             torch::Tensor w);
+                             torch::Tensor w, int64_t persistent);
+int64_t skinny_persistent_pin(int64_t pin);
 void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                         torch::Tensor counts, torch::Tensor offsets);
 void gemm_skinny_w8_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w_q,
@@ -110,12 +112,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_skinny_bf16", &gemm_skinny_bf16,
         "skinny-M (M<=16) bf16 MFMA weight-streaming GEMM; tiles_per_wg "
         "pins the N-tiles per workgroup (1/2/4), unroll the k-chunks in "
-        "flight (4/8; 8 needs K % 1024 == 0); 0 = auto",
+        "flight (4/8; 8 needs K % 1024 == 0); 0 = auto. persistent pins "
+        "the one-workgroup-per-CU kernel with the activation in LDS off (0) "
+        "or on (1; needs K <= 4096 and tiles_per_wg = unroll = 0); -1 = auto",
         py::arg("out"), py::arg("x"), py::arg("w"),
-        py::arg("tiles_per_wg") = 0, py::arg("unroll") = 0);
+        py::arg("tiles_per_wg") = 0, py::arg("unroll") = 0,
+        py::arg("persistent") = -1);
   m.def("gemm_skinny_swiglu_bf16", &gemm_skinny_swiglu_bf16,
         "skinny-M gate_up GEMM with fused SwiGLU epilogue: "
-        "out[M,I] = silu(x Wg^T) * (x Wu^T), w = [Wg; Wu]");
+        "out[M,I] = silu(x Wg^T) * (x Wu^T), w = [Wg; Wu]; persistent as "
+        "for gemm_skinny_bf16",
+        py::arg("out"), py::arg("x"), py::arg("w"),
+        py::arg("persistent") = -1);
+  m.def("skinny_persistent_pin", &skinny_persistent_pin,
+        "pin the persistent skinny GEMM for every call that does not pin it "
+        "itself: -1 the measured rule, 0 off, 1 on (where K fits); returns "
+        "the previous pin, which starts from DTS_SKINNY_PERSISTENT",
+        py::arg("pin"));
   m.def("moe_grouped_linear", &moe_grouped_linear,
         "grouped per-expert skinny GEMM (capture-safe MoE decode)");
   m.def("gemm_skinny_w8_bf16", &gemm_skinny_w8_bf16,

@@ -26,6 +26,8 @@
 #include "common.h"
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <ATen/hip/HIPContext.h>
+#include <atomic>
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -148,6 +150,221 @@ gemm_skinny_kernel(short* __restrict__ out,      // [M, N] (row stride out_ts)
           out[(long)m * out_ts + n] = f2bf(v);
         }
       }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Persistent form: one 16-wave workgroup per CU, activation staged in LDS.
+//
+// gemm_skinny_kernel pulls the whole M x K activation through L2 -> L1 once
+// per workgroup, on the same vector-memory path as the weights (gate_up at
+// M=8: 896 x 64 KB = 57 MB beside 235 MB of W). Here a workgroup copies
+// x[M, K] into LDS ONCE and then walks its share of the tiles with only
+// weight loads on the vector-memory path; A fragments are one 16 B LDS read
+// per lane and chunk.
+//
+// The workgroup is PERSIST_T teams of NWAVES waves; a team is
+// gemm_skinny_kernel's workgroup unchanged: wave w owns K-quarter w, walks
+// its 32-k chunks in ascending order into one accumulator per tile, and the
+// four partials are summed wave0 + wave1 + wave2 + wave3 (wave 0 keeps its
+// own partial in registers, which is the same left-to-right sum as
+// red[0]+red[1]+red[2]+red[3]) before ONE f2bf — so every output element is
+// bit-identical to gemm_skinny_kernel's.
+//
+// Unit u is one N-tile (W rows 16u..16u+15) or, for SwiGLU, the gate tile
+// u and its up tile (rows I + 16u..). Slot s = trip * PERSIST_T + team of
+// workgroup b owns unit s * gridDim.x + b: static, no cross-workgroup
+// dependency, and every workgroup gets the same number of units +-1.
+// Barriers are workgroup-wide, so every team runs the same `trips` loop
+// trips; a team without a unit loads and stores nothing.
+//
+// LDS image: row m at short offset m * (K + 8). Rows >= M are never
+// written or read (their A fragment is zero). K % 512 == 0 makes the plain
+// 2K-byte row stride a multiple of 1024 B, i.e. all 16 rows of a fragment
+// read would hit the same banks (16-way conflict); the 16 B pad shifts row
+// m by 4 banks, so the 16 lanes of one ds_read_b128 phase (rows 0..15, same
+// k) cover 16 x 16 B = all 64 banks exactly once: 0 conflicts, derived.
+// Budget at K = 4096: 16 x 4104 x 2 = 131,328 B image + 24 KB reduction
+// (plain: 2 buffers x 4 teams x 3 waves x 1 KB, one barrier per trip;
+// SwiGLU: 1 buffer x 4 teams x 2 tiles x 3 waves x 1 KB, two barriers) =
+// 155,904 B of the CU's 160 KB.
+// ---------------------------------------------------------------------------
+
+#define PERSIST_T 4        // teams per workgroup
+#define PERSIST_KMAX 4096  // largest K whose image fits
+#define PERSIST_PAD 8      // bf16 of padding per image row
+// byte offset a lane without a W row loads from; W must end at or below it
+#define PERSIST_DEAD_OFF 0x80000000u
+
+template <int KU, bool SWIGLU>
+__global__ void __launch_bounds__(PERSIST_T* NWAVES* WAVE)
+gemm_skinny_persistent_kernel(short* __restrict__ out,      // [M, N | I]
+                              const short* __restrict__ x,  // [M, K]
+                              const short* __restrict__ w,  // [N, K]
+                              int M, int N, int K, long x_ts, long out_ts,
+                              int units, int tile_stride) {
+  constexpr int NT = SWIGLU ? 2 : 1;
+  constexpr int NBUF = SWIGLU ? 1 : 2;
+  __shared__ __attribute__((aligned(16))) short
+      ximg[16 * (PERSIST_KMAX + PERSIST_PAD)];
+  __shared__ float red[NBUF][PERSIST_T][NT][NWAVES - 1][16][16];
+
+  const int team = threadIdx.x / (NWAVES * WAVE);
+  const int wave = (threadIdx.x / WAVE) % NWAVES;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int ld = K + PERSIST_PAD;
+  const int slots = gridDim.x * PERSIST_T;
+  const int trips = (units + slots - 1) / slots;
+
+  const int kq = K / NWAVES;
+  const int kbeg = wave * kq;
+  const int kend = kbeg + kq;
+  const int a_row = lane & 15;
+  const int k_off = (lane >> 4) * 8;
+  const bool a_live = a_row < M;
+  const short* arow = ximg + a_row * ld;
+  const int c_col = lane & 15;
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  // Weights come through a raw buffer resource over W: a lane without a
+  // row (dead unit, row >= N) gets the offset DEAD, which lies past the
+  // buffer, so the hardware's range check returns zero for it instead of
+  // loading. That keeps the load stream free of branches, so the compiler
+  // can count loads in flight and wait for the older group only. The host
+  // checks N * K * 2 <= PERSIST_DEAD_OFF: every live offset is below DEAD,
+  // and DEAD plus any k offset (< 2 * PERSIST_KMAX + 64 bytes) stays below
+  // 2^32, so a dead lane's offset never wraps back into the buffer.
+  const __amdgpu_buffer_rsrc_t wbuf = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)w, 0, (int)((unsigned)N * (unsigned)K * 2u), 0x00020000);
+  constexpr unsigned DEAD = PERSIST_DEAD_OFF;
+  int n0 = 0;
+  bool u_live = false;
+  unsigned woff[NT];  // byte offset of this lane's W row, or DEAD
+  auto set_unit = [&](int trip) __attribute__((always_inline)) {
+    const int u = (trip * PERSIST_T + team) * gridDim.x + blockIdx.x;
+    u_live = trip < trips && u < units;
+    n0 = u * 16;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int b_row = n0 + j * tile_stride + (lane & 15);
+      woff[j] = (u_live && b_row < N)
+                    ? (unsigned)b_row * (unsigned)K * 2u + k_off * 2u
+                    : DEAD;
+    }
+  };
+  auto load_b = [&](int k0, bf16x8 (&b)[NT][KU])
+                    __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < KU; ++u)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const unsigned off = woff[j] + (unsigned)(k0 + u * KSTEP) * 2u;
+        b[j][u] = __builtin_bit_cast(
+            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wbuf, off, 0, 0));
+      }
+  };
+
+  // Stage x: every load is issued before the first LDS write (at most
+  // 16 * PERSIST_KMAX / 8 vectors over 1024 threads = 8 per thread), and
+  // the first unit's first weight group is issued behind them, so it
+  // stays in flight while the image is written.
+  constexpr int NTHREADS = PERSIST_T * NWAVES * WAVE;
+  constexpr int NSTAGE = 16 * PERSIST_KMAX / 8 / NTHREADS;
+  const int kvec = K / 8;
+  bf16x8 st[NSTAGE];
+#pragma unroll
+  for (int i = 0; i < NSTAGE; ++i) {
+    const int v = threadIdx.x + i * NTHREADS;
+    const int m = v / kvec, c = (v - m * kvec) * 8;
+    st[i] = v < M * kvec ? *(const bf16x8*)(x + (long)m * x_ts + c) : zero8;
+  }
+  bf16x8 b0[NT][KU], b1[NT][KU];
+  set_unit(0);
+  load_b(kbeg, b0);
+#pragma unroll
+  for (int i = 0; i < NSTAGE; ++i) {
+    const int v = threadIdx.x + i * NTHREADS;
+    const int m = v / kvec, c = (v - m * kvec) * 8;
+    if (v < M * kvec) *(bf16x8*)(ximg + m * ld + c) = st[i];
+  }
+  __syncthreads();
+
+  // One flat loop over every weight group of every trip, two groups in
+  // flight: while group g is consumed from `cur`, group g + 1 — of the same
+  // unit, or the first of the team's next unit, which then flies over the
+  // reduction — is already loading into `nxt`. The two buffers swap roles
+  // by calling step() with them exchanged, not by copying.
+  constexpr int GROUP = KSTEP * KU;
+  const int ngroups = kq / GROUP;
+  const int total = trips * ngroups;
+  int cur_n0 = n0;
+  bool cur_live = u_live;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = {0.f, 0.f, 0.f, 0.f};
+
+  auto step = [&](int kg, int trip, const bf16x8 (&cur)[NT][KU],
+                  bf16x8 (&nxt)[NT][KU]) __attribute__((always_inline)) {
+    const bool last = kg + 1 == ngroups;
+    const int k0 = kbeg + kg * GROUP;
+    if (last) set_unit(trip + 1);
+    load_b(last ? kbeg : k0 + GROUP, nxt);
+    bf16x8 a[KU];
+#pragma unroll
+    for (int u = 0; u < KU; ++u)
+      a[u] = a_live ? *(const bf16x8*)(arow + k0 + u * KSTEP + k_off) : zero8;
+#pragma unroll
+    for (int u = 0; u < KU; ++u)
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], cur[j][u],
+                                                         acc[j], 0, 0, 0);
+    if (!last) return;
+    // the unit is complete: reduce the team's four partials and store
+    const int buf = trip & (NBUF - 1);
+    if (wave != 0) {
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          red[buf][team][j][wave - 1][(lane >> 4) * 4 + i][c_col] = acc[j][i];
+    }
+    __syncthreads();
+    if (wave == 0 && cur_live) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = (lane >> 4) * 4 + i;
+        float v[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+          v[j] = acc[j][i] + red[buf][team][j][0][m][c_col] +
+                 red[buf][team][j][1][m][c_col] +
+                 red[buf][team][j][2][m][c_col];
+        const int n = cur_n0 + c_col;
+        if constexpr (SWIGLU) {
+          if (m < M && n < tile_stride)
+            out[(long)m * out_ts + n] = swiglu_bf16(f2bf(v[0]), f2bf(v[1]));
+        } else {
+          if (m < M && n < N) out[(long)m * out_ts + n] = f2bf(v[0]);
+        }
+      }
+    }
+    // one reduction buffer: it is rewritten next trip, so readers finish
+    // first; with two, the barrier of trip t+1 already orders trip t's
+    // reads before trip t+2's writes
+    if constexpr (NBUF == 1) __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = {0.f, 0.f, 0.f, 0.f};
+    cur_n0 = n0;
+    cur_live = u_live;
+  };
+  for (int g = 0, kg = 0, trip = 0; g < total; g += 2) {
+    step(kg, trip, b0, b1);
+    if (++kg == ngroups) kg = 0, ++trip;
+    if (g + 1 < total) {
+      step(kg, trip, b1, b0);
+      if (++kg == ngroups) kg = 0, ++trip;
     }
   }
 }
@@ -305,8 +522,88 @@ static int skinny_auto_tiles(int M, int tiles) {
   return 1;
 }
 
+// Whether a call takes the persistent kernel. `persistent` is the binding's
+// pin (-1 auto, 0 off, 1 on); DTS_SKINNY_PERSISTENT=0|1 pins it process-wide
+// for A/B runs; unset means the measured rule. An explicit pin on a K whose
+// LDS image does not fit is an error; the env pin and the rule fall back to
+// gemm_skinny_kernel there, and so does a call that pins tiles_per_wg or
+// unroll, which name that kernel's variants.
+//
+// Measured rule (cold weights cycled past the Infinity Cache, MI355X, 256
+// CUs, profiles/microbench_skinny_persistent.jsonl; current auto path ->
+// persistent, us, median of 5 alternating rounds, spreads <= 1.0): the
+// persistent path is taken only where it wins by more than 3x the larger
+// spread.
+//   lm_head (8016 tiles)  M=1 169.3 -> 174.0, M=4 184.5 -> 178.9,
+//                         M=8 204.5 -> 184.8, M=16 223.3 -> 195.0
+//   gate_up (1792 tiles)  M=1 40.4 -> 43.0, M=4 44.4 -> 44.4,
+//                         M=8 52.0 -> 44.2, M=16 56.9 -> 45.2
+//   gate_up SwiGLU (896 pairs)  M=1 45.8 -> 44.0, M=4 48.9 -> 45.0,
+//                         M=8 52.7 -> 46.0, M=16 59.9 -> 47.1
+//   qkv (384 tiles)       M=1 12.6 -> 13.9, M=4 13.5 -> 14.0,
+//                         M=8 14.8 -> 15.1, M=16 16.2 -> 16.4: never —
+//                         1.5 tiles per CU leave half the teams idle
+// Only these K=4096 shapes were timed, and at a smaller K the fixed cost of
+// staging and of the barriers weighs more, so the rule selects nothing at
+// another K and no unit count below the one measured; M between the
+// measured points takes the band of the next lower one.
+static bool skinny_persistent_rule(int M, int K, int units, bool swiglu) {
+  if (K != 4096) return false;
+  if (swiglu) return units >= 896;
+  if (units >= 8016) return M >= 4;
+  if (units >= 1792) return M >= 8;
+  return false;
+}
+
+// Process-wide pin: -1 the measured rule, 0 off, 1 on. A knob for tests and
+// A/B runs, not for tuning: 1 sends EVERY skinny GEMM whose K fits through
+// the persistent kernel, qkv and o_proj included, which lose there. It
+// starts from
+// DTS_SKINNY_PERSISTENT and can be changed with skinny_persistent_pin(), so
+// one process can run both paths (a captured graph keeps the kernel it
+// was captured with).
+static std::atomic<int> g_persist_pin{[] {
+  const char* e = getenv("DTS_SKINNY_PERSISTENT");
+  return (e && e[0] == '1') ? 1 : (e && e[0] == '0') ? 0 : -1;
+}()};
+
+int64_t skinny_persistent_pin(int64_t pin) {
+  TORCH_CHECK(pin >= -1 && pin <= 1, "pin must be -1 (rule), 0 or 1");
+  return g_persist_pin.exchange((int)pin);
+}
+
+static bool skinny_use_persistent(int64_t persistent, bool other_pins, int M,
+                                  int N, int K, int units, bool swiglu) {
+  const int env_p = g_persist_pin.load();
+  TORCH_CHECK(persistent >= -1 && persistent <= 1,
+              "persistent must be -1 (auto), 0 or 1");
+  // the image lives in LDS, and W is addressed by 32-bit buffer offsets
+  // that must stay below the one dead lanes use
+  const bool fits =
+      K <= PERSIST_KMAX && (int64_t)N * K * 2 <= (int64_t)PERSIST_DEAD_OFF;
+  TORCH_CHECK(persistent != 1 || fits, "persistent=1 needs K <= ",
+              PERSIST_KMAX, " and a weight of at most 2 GiB, got K=", K, " N=", N);
+  if (persistent >= 0) return persistent == 1;
+  if (other_pins || !fits) return false;
+  if (env_p >= 0) return env_p == 1;
+  return skinny_persistent_rule(M, K, units, swiglu);
+}
+
+// The grid is one workgroup per CU: 1024 threads and 156 KB of LDS leave
+// room for no second one, and the static tile map is balanced on that
+// assumption only (nothing breaks otherwise: workgroups do not depend on
+// each other).
+#define PERSIST_LAUNCH(KU_, SW_, units_, ts_)                                \
+  hipLaunchKernelGGL(                                                        \
+      (gemm_skinny_persistent_kernel<KU_, SW_>),                             \
+      dim3(at::cuda::getCurrentDeviceProperties()->multiProcessorCount),     \
+      dim3(PERSIST_T* NWAVES* WAVE), 0, stream, (short*)out.data_ptr(),      \
+      (const short*)x.data_ptr(), (const short*)w.data_ptr(), M, N, K,       \
+      x.stride(0), out.stride(0), units_, ts_)
+
 void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                      int64_t tiles_per_wg, int64_t unroll) {
+                      int64_t tiles_per_wg, int64_t unroll,
+                      int64_t persistent) {
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(w.is_contiguous(), "weight must be contiguous [N, K]");
   TORCH_CHECK(x.stride(1) == 1, "x rows must be dense");
@@ -323,10 +620,20 @@ void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(unroll == 0 || unroll == 4 || unroll == 8,
               "unroll must be 0 (auto), 4 or 8");
   const int tiles = (N + 15) / 16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  if (skinny_use_persistent(persistent, tiles_per_wg != 0 || unroll != 0, M,
+                            N, K, tiles, false)) {
+    // one variant: a team takes one tile per trip and keeps two groups
+    // of KUNROLL chunks in flight (8 per group spills at 1024 threads)
+    TORCH_CHECK(tiles_per_wg == 0 && unroll == 0,
+                "persistent=1 has no tiles_per_wg or unroll variants");
+    PERSIST_LAUNCH(KUNROLL, false, tiles, 16);
+    HIP_CHECK_LAST();
+    return;
+  }
   const int nt =
       tiles_per_wg ? (int)tiles_per_wg : skinny_auto_tiles(M, tiles);
   const int grid = (tiles + nt - 1) / nt;
-  auto stream = c10::hip::getCurrentHIPStream();
   if (skinny_unroll(K, unroll) == 8) {
     if (nt == 4) SKINNY_LAUNCH(8, 4, false, grid, 64, 16);
     else if (nt == 2) SKINNY_LAUNCH(8, 2, false, grid, 32, 16);
@@ -342,7 +649,7 @@ void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 // out[M, I] = silu(x @ Wg^T) * (x @ Wu^T) with w = [Wg ; Wu] of shape
 // [2I, K]: the gate_up projection and the SwiGLU activation in one pass.
 void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
-                             torch::Tensor w) {
+                             torch::Tensor w, int64_t persistent) {
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(w.is_contiguous(), "weight must be contiguous [2I, K]");
   TORCH_CHECK(x.stride(1) == 1, "x rows must be dense");
@@ -357,6 +664,11 @@ void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
   TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == I);
   const int grid = I / 16;
   auto stream = c10::hip::getCurrentHIPStream();
+  if (skinny_use_persistent(persistent, false, M, N, K, grid, true)) {
+    PERSIST_LAUNCH(KUNROLL, true, grid, I);
+    HIP_CHECK_LAST();
+    return;
+  }
   if (skinny_unroll(K, 0) == 8)
     SKINNY_LAUNCH(8, 2, true, grid, 16, I);
   else
@@ -364,3 +676,4 @@ void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
   HIP_CHECK_LAST();
 }
 #undef SKINNY_LAUNCH
+#undef PERSIST_LAUNCH

@@ -373,7 +373,93 @@ def kv_fp8_probes(ext):
             del k16, v16, k8, v8
 
 
+def persistent_probes(ext):
+    """Persistent skinny GEMM (one workgroup per CU, activation in LDS)
+    against the current auto dispatch with the persistent path pinned off,
+    on the K=4096 Llama-3-8B shapes: qkv, gate_up (plain and fused SwiGLU)
+    and lm_head at M = 1, 4, 8, 16. The two alternate in this process, five
+    rounds each; every figure is the median round and *_spread_us is
+    max - min. Weights cycle through enough copies to exceed the 256 MB
+    Infinity Cache."""
+    dev = "cuda"
+    bf16 = torch.bfloat16
+    shapes = (("qkv", 4096, 6144), ("gate_up", 4096, 28672),
+              ("lm_head", 4096, 128256))
+    rounds = 5
+
+    def med(ts):
+        return round(sorted(ts)[len(ts) // 2], 1), round(max(ts) - min(ts), 1)
+
+    for name, K, N in shapes:
+        copies = max(2, min(8, (1 << 30) // (N * K * 2) + 1))
+        ws = [torch.randn(N, K, dtype=bf16, device=dev) for _ in range(copies)]
+        for M in (1, 4, 8, 16):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            out = torch.empty(M, N, dtype=bf16, device=dev)
+            act = torch.empty(M, N // 2, dtype=bf16, device=dev)
+            fns = {
+                "current": lambda i: ext.gemm_skinny_bf16(
+                    out, x, ws[i], persistent=0),
+                "persistent": lambda i: ext.gemm_skinny_bf16(
+                    out, x, ws[i], persistent=1),
+            }
+            if name == "gate_up":
+                fns["swiglu_current"] = lambda i: ext.gemm_skinny_swiglu_bf16(
+                    act, x, ws[i], persistent=0)
+                fns["swiglu_persistent"] = lambda i: ext.gemm_skinny_swiglu_bf16(
+                    act, x, ws[i], persistent=1)
+
+                def plain_plus_silu(i):
+                    ext.gemm_skinny_bf16(out, x, ws[i], persistent=1)
+                    ext.silu_mul(act, out)
+
+                fns["persistent_plus_silu_mul"] = plain_plus_silu
+            ts = {k: [] for k in fns}
+            for _ in range(rounds):
+                for k, fn in fns.items():
+                    ts[k].append(_time_us(fn, copies, reps=1))
+            rec = {"probe": f"skinny_persistent_{name}_M{M}_K{K}_N{N}",
+                   "copies": copies}
+            for k in fns:
+                rec[f"{k}_us"], rec[f"{k}_spread_us"] = med(ts[k])
+            rec["persistent_TBps"] = round(
+                N * K * 2 / rec["persistent_us"] / 1e6, 2)
+            print(json.dumps(rec), flush=True)
+        del ws
+
+
+def persistent_pmc_target(ext, which):
+    """The target of a counter run: the Llama-3-8B gate_up at M=8, plain and
+    fused SwiGLU, four calls each on four different weights, with the
+    persistent path pinned off (which = 'current') or on ('persistent')."""
+    pin = {"current": 0, "persistent": 1}[which]
+    K, N, M = 4096, 28672, 8
+    bf16 = torch.bfloat16
+    ws = [torch.randn(N, K, dtype=bf16, device="cuda") for _ in range(4)]
+    x = torch.randn(M, K, dtype=bf16, device="cuda")
+    out = torch.empty(M, N, dtype=bf16, device="cuda")
+    act = torch.empty(M, N // 2, dtype=bf16, device="cuda")
+    for w in ws:
+        ext.gemm_skinny_bf16(out, x, w, persistent=pin)
+    for w in ws:
+        ext.gemm_skinny_swiglu_bf16(act, x, w, persistent=pin)
+    torch.cuda.synchronize()
+
+
 def main():
+    if "--persistent-pmc" in sys.argv:
+        # python scripts/microbench.py --persistent-pmc current|persistent
+        from dts_amd.ops import _hip_ext_loader
+
+        persistent_pmc_target(
+            _hip_ext_loader.load(), sys.argv[sys.argv.index("--persistent-pmc") + 1]
+        )
+        return
+    if "--persistent-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        persistent_probes(_hip_ext_loader.load())
+        return
     if "--kv-fp8-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
 
