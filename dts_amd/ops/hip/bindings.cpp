@@ -112,7 +112,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_skinny_bf16", &gemm_skinny_bf16,
         "skinny-M (M<=16) bf16 MFMA weight-streaming GEMM; tiles_per_wg "
         "pins the N-tiles per workgroup (1/2/4), unroll the k-chunks in "
-        "flight (4/8; 8 needs K % 1024 == 0); 0 = auto. persistent pins "
+        "flight (4/8; 8 needs K % 1024 == 0; 16/32 name the stream kernel's "
+        "ring of loads: K % 1024 == 0, tiles_per_wg 1, or 2 at 16, operands "
+        "of at most 2 GiB); 0 = auto. persistent pins "
         "the one-workgroup-per-CU kernel with the activation in LDS off (0) "
         "or on (1; needs K <= 4096 and tiles_per_wg = unroll = 0); -1 = auto",
         py::arg("out"), py::arg("x"), py::arg("w"),

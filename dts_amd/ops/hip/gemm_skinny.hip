@@ -27,6 +27,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <ATen/hip/HIPContext.h>
+#include <algorithm>
 #include <atomic>
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
@@ -370,6 +371,155 @@ gemm_skinny_persistent_kernel(short* __restrict__ out,      // [M, N | I]
 }
 
 // ---------------------------------------------------------------------------
+// Stream form: gemm_skinny_kernel's workgroup with a deep ring of loads.
+//
+// o, qkv and down have one 4-wave workgroup per CU or fewer: one wave per
+// SIMD, nothing else to hide a wait, and gemm_skinny_kernel loads a group
+// of KU chunks, uses all of them, then loads the next — the bytes a wave
+// has in flight (KU KB) bound its rate. Here wave w keeps a ring of NG
+// groups of GC chunks in flight over its K-quarter: the prologue requests
+// NG groups; a step waits for the OLDEST group only, runs its MFMAs and
+// requests the group NG ahead into the registers it has just freed. The
+// ring positions are unrolled, so the register arrays are indexed
+// statically and nothing is copied. Nothing is requested past the
+// quarter's end.
+//
+// The arithmetic per output element is gemm_skinny_kernel's: wave w owns
+// K-quarter w, its 32-k chunks go in ascending order into ONE accumulator
+// per tile, the partials are summed red[0]+red[1]+red[2]+red[3] and
+// rounded once — bit-identical.
+//
+// W and x both come through raw buffer resources, as W does in the
+// persistent kernel: a lane without a row (W row >= N, x row >= M) gets
+// the offset STREAM_DEAD_OFF, which lies at or past the end of either
+// buffer, so the range check returns zero for it and the load stream has
+// no branch; only then can the compiler count the loads in flight and
+// wait with a non-zero vmcnt. The host checks that W and the x view are
+// at most 2 GiB each: every live offset is then below the dead one, and
+// the dead one plus any k offset (< 2 K bytes <= 2 GiB) stays below 2^32.
+// ---------------------------------------------------------------------------
+
+#define STREAM_GC 8  // chunks per group: the host needs K % 1024 == 0
+#define STREAM_DEAD_OFF 0x80000000u
+
+template <int GC, int NG, int NT>
+__global__ void __launch_bounds__(NWAVES* WAVE)
+gemm_skinny_stream_kernel(short* __restrict__ out,      // [M, N] (out_ts)
+                          const short* __restrict__ x,  // [M, K] (x_ts)
+                          const short* __restrict__ w,  // [N, K]
+                          int M, int N, int K, long x_ts, long out_ts,
+                          int wg_stride, int tile_stride) {
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int n0 = blockIdx.x * wg_stride;
+  const int kq = K / NWAVES;
+  const int kbeg = wave * kq;
+  const int a_row = lane & 15;
+  const int k_off = (lane >> 4) * 8;
+
+  const __amdgpu_buffer_rsrc_t wbuf = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)w, 0, (int)((unsigned)N * (unsigned)K * 2u), 0x00020000);
+  // the x view ends with row M-1; rows past it are outside the resource
+  const __amdgpu_buffer_rsrc_t xbuf = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)x, 0, (int)(unsigned)(((long)(M - 1) * x_ts + K) * 2), 0x00020000);
+  constexpr unsigned DEAD = STREAM_DEAD_OFF;
+  // byte offsets of this lane's x row and W rows at the quarter's start
+  const unsigned kb0 = (unsigned)(kbeg + k_off) * 2u;
+  const unsigned xoff =
+      a_row < M ? (unsigned)((long)a_row * x_ts * 2) + kb0 : DEAD;
+  unsigned woff[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int b_row = n0 + j * tile_stride + (lane & 15);
+    woff[j] = b_row < N ? (unsigned)b_row * (unsigned)K * 2u + kb0 : DEAD;
+  }
+
+  f32x4 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = {0.f, 0.f, 0.f, 0.f};
+
+  constexpr int GROUP = KSTEP * GC;
+  const int ngroups = kq / GROUP;
+  auto issue = [&](int g, bf16x8 (&a)[GC], bf16x8 (&b)[NT][GC])
+                   __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < GC; ++u) {
+      const unsigned kb = (unsigned)(g * GROUP + u * KSTEP) * 2u;
+      a[u] = __builtin_bit_cast(
+          bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xbuf, xoff + kb, 0, 0));
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        b[j][u] = __builtin_bit_cast(
+            bf16x8,
+            __builtin_amdgcn_raw_buffer_load_b128(wbuf, woff[j] + kb, 0, 0));
+    }
+  };
+  auto consume = [&](const bf16x8 (&a)[GC], const bf16x8 (&b)[NT][GC])
+                     __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < GC; ++u)
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[j][u], acc[j],
+                                                         0, 0, 0);
+  };
+
+  bf16x8 a[NG][GC], b[NG][NT][GC];
+  if (ngroups >= NG) {
+#pragma unroll
+    for (int r = 0; r < NG; ++r) issue(r, a[r], b[r]);
+    // steady state, free of branches: every step refills its ring position
+    int g = 0;
+    for (; g + 2 * NG <= ngroups; g += NG) {
+#pragma unroll
+      for (int r = 0; r < NG; ++r) {
+        consume(a[r], b[r]);
+        issue(g + r + NG, a[r], b[r]);
+      }
+    }
+    // NG .. 2 NG - 1 groups are left and the last NG of them are in flight:
+    // the first steps still refill, the rest drain the ring
+#pragma unroll
+    for (int t = 0; t < 2 * NG - 1; ++t) {
+      if (g + t < ngroups) {
+        consume(a[t % NG], b[t % NG]);
+        if (g + t + NG < ngroups) issue(g + t + NG, a[t % NG], b[t % NG]);
+      }
+    }
+  } else {
+    // a quarter shorter than the ring: request all of it, then use it
+#pragma unroll
+    for (int r = 0; r < NG - 1; ++r)
+      if (r < ngroups) issue(r, a[r], b[r]);
+#pragma unroll
+    for (int r = 0; r < NG - 1; ++r)
+      if (r < ngroups) consume(a[r], b[r]);
+  }
+
+  // gemm_skinny_kernel's reduction and store
+  __shared__ float red[NT][NWAVES][16][16];
+  const int c_col = lane & 15;
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      red[j][wave][(lane >> 4) * 4 + i][c_col] = acc[j][i];
+  __syncthreads();
+  for (int j = wave; j < NT; j += NWAVES) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = (lane >> 4) * 4 + i;
+      const int n = n0 + j * tile_stride + c_col;
+      if (m < M && n < N) {
+        float v = red[j][0][m][c_col] + red[j][1][m][c_col] +
+                  red[j][2][m][c_col] + red[j][3][m][c_col];
+        out[(long)m * out_ts + n] = f2bf(v);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Grouped skinny GEMM for MoE decode (capture-safe expert dispatch).
 //
 // out[p, :] = x[p, :] @ W[e, :, :]^T for rows p in expert e's contiguous
@@ -478,12 +628,20 @@ void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 // chunks and a 256-workgroup grid has no other waves to hide the latency —
 // and is flat-to-worse on the K=4096 shapes (qkv 15.2 -> 15.9), so auto is
 // 8 for K >= 8192. DTS_SKINNY_UNROLL=4|8 pins it process-wide for A/B;
-// unset now means this auto rule (it used to mean 4).
-static int skinny_unroll(int K, int64_t unroll) {
+// unset now means this auto rule (it used to mean 4). 16 and 32 there name
+// the stream kernel (skinny_stream_chunks below) and leave this kernel on
+// its auto rule.
+static int skinny_env_unroll() {
   static const int env_ku = [] {
     const char* e = getenv("DTS_SKINNY_UNROLL");
-    return (e && e[0] == '8') ? 8 : (e && e[0] == '4') ? 4 : 0;
+    const int n = e ? atoi(e) : 0;
+    return (n == 4 || n == 8 || n == 16 || n == 32) ? n : 0;
   }();
+  return env_ku;
+}
+
+static int skinny_unroll(int K, int64_t unroll) {
+  const int env_ku = skinny_env_unroll() <= 8 ? skinny_env_unroll() : 0;
   // an explicit unroll=8 on a K that is no multiple of 1024 is an error;
   // the env pin and the auto rule fall back to 4 there
   TORCH_CHECK(unroll != 8 || K % (NWAVES * KSTEP * 8) == 0,
@@ -493,11 +651,88 @@ static int skinny_unroll(int K, int64_t unroll) {
   return ku;
 }
 
+// Measured rule for the stream kernel: chunks in flight per wave (and the
+// tiles per workgroup in *nt) where it beats the current auto path by more
+// than 3x the larger spread, else 0. Cold weights cycled past the Infinity
+// Cache, MI355X, 256 CUs, profiles/microbench_skinny_stream.jsonl; current
+// auto path -> stream, us, median of 5 alternating rounds, every spread
+// <= 0.1:
+//   o (K=4096, 256 tiles), 16 chunks, NT=1:
+//                 M=1 10.1 -> 7.6, M=4 10.6 -> 8.3, M=6 10.6 -> 8.4,
+//                 M=8 10.8 -> 8.6, M=16 11.4 -> 10.0 (32 chunks: 9.8, no
+//                 clear difference)
+//   qkv (K=4096, 384 tiles), 16 chunks, NT=2 (NT=1 gains <= 0.3 below M=16
+//                 and loses there):
+//                 M=1 12.0 -> 11.9: no; M=4 13.4 -> 12.5, M=6 14.0 -> 12.8,
+//                 M=8 14.6 -> 13.4, M=16 16.1 -> 14.9
+//   down (K=14336, 256 tiles), 16 chunks, NT=1:
+//                 M=1 23.7 -> 21.7, M=4 24.3 -> 23.5; M=6 24.8 -> 24.6,
+//                 M=8 26.0 -> 26.1, M=16 31.4 -> 32.0: no
+// 32 chunks in flight never beat 16 by more than the spread (qkv: 1 us
+// slower), so the rule does not select them. Only these three (K, tile
+// count) pairs were timed, so nothing else is selected; M between the
+// measured points takes the band of the next lower one.
+static int skinny_auto_tiles(int M, int tiles);
+
+static int skinny_stream_rule(int M, int K, int tiles, int* nt) {
+  *nt = 1;
+  if (K == 4096 && tiles == 256) return 16;
+  if (K == 4096 && tiles == 384 && M >= 4) return *nt = 2, 16;
+  if (K == 14336 && tiles == 256 && M < 6) return 16;
+  return 0;
+}
+
+// Tiles per workgroup the stream kernel is built with at `chunks` in
+// flight: 32 chunks of two tiles are 96 loads, and a wave counts 64.
+static int skinny_stream_max_tiles(int chunks) { return chunks == 16 ? 2 : 1; }
+
+// Chunks in flight per wave if this call takes the stream kernel, else 0.
+// unroll=16|32 pins it, and is an error where K, tiles_per_wg or the buffer
+// sizes do not fit; DTS_SKINNY_UNROLL=16|32 and the measured rule apply to
+// calls that pin neither unroll nor tiles_per_wg, and fall back to
+// gemm_skinny_kernel where something does not fit. *nt is the tiles per
+// workgroup: the pinned value, the rule's, or under the env pin what
+// skinny_auto_tiles picks as far as the variant exists.
+static int skinny_stream_chunks(int64_t unroll, int64_t tiles_per_wg, int M,
+                                int N, int K, int tiles, long x_ts, int* nt) {
+  const bool k_ok = K % (NWAVES * KSTEP * STREAM_GC) == 0;
+  // both buffers are addressed by 32-bit offsets that must stay below the
+  // one dead lanes use
+  const bool fits =
+      (int64_t)N * K * 2 <= (int64_t)STREAM_DEAD_OFF &&
+      ((int64_t)(M - 1) * x_ts + K) * 2 <= (int64_t)STREAM_DEAD_OFF;
+  if (unroll == 16 || unroll == 32) {
+    TORCH_CHECK(k_ok, "unroll=", unroll, " needs K % 1024 == 0, got K=", K);
+    TORCH_CHECK(tiles_per_wg <= skinny_stream_max_tiles((int)unroll),
+                "unroll=", unroll, " has no tiles_per_wg=", tiles_per_wg,
+                " variant");
+    TORCH_CHECK(fits, "unroll=", unroll,
+                " needs a weight and an x view of at most 2 GiB each");
+    *nt = tiles_per_wg ? (int)tiles_per_wg
+                       : std::min(skinny_auto_tiles(M, tiles),
+                                  skinny_stream_max_tiles((int)unroll));
+    return (int)unroll;
+  }
+  if (unroll != 0 || tiles_per_wg != 0 || !k_ok || !fits) return 0;
+  const int env = skinny_env_unroll();
+  if (!env) return skinny_stream_rule(M, K, tiles, nt);
+  if (env <= 8) return 0;
+  *nt = std::min(skinny_auto_tiles(M, tiles), skinny_stream_max_tiles(env));
+  return env;
+}
+
 #define SKINNY_LAUNCH(KU_, NT_, SW_, grid_, wgs_, ts_)                        \
   hipLaunchKernelGGL((gemm_skinny_kernel<KU_, NT_, SW_>), dim3(grid_),       \
                      dim3(NWAVES * WAVE), 0, stream, (short*)out.data_ptr(), \
                      (const short*)x.data_ptr(), (const short*)w.data_ptr(), \
                      M, N, K, x.stride(0), out.stride(0), wgs_, ts_)
+
+#define STREAM_LAUNCH(NG_, NT_, grid_, wgs_)                                  \
+  hipLaunchKernelGGL((gemm_skinny_stream_kernel<STREAM_GC, NG_, NT_>),       \
+                     dim3(grid_), dim3(NWAVES* WAVE), 0, stream,             \
+                     (short*)out.data_ptr(), (const short*)x.data_ptr(),     \
+                     (const short*)w.data_ptr(), M, N, K, x.stride(0),       \
+                     out.stride(0), wgs_, 16)
 
 // Tiles per workgroup (NT), measured rule (cold weights, MI355X,
 // profiles/microbench_decode_kernels_nt_sweep.jsonl; us at NT=1 -> best):
@@ -617,8 +852,9 @@ void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(tiles_per_wg == 0 || tiles_per_wg == 1 || tiles_per_wg == 2 ||
                   tiles_per_wg == 4,
               "tiles_per_wg must be 0 (auto), 1, 2 or 4");
-  TORCH_CHECK(unroll == 0 || unroll == 4 || unroll == 8,
-              "unroll must be 0 (auto), 4 or 8");
+  TORCH_CHECK(unroll == 0 || unroll == 4 || unroll == 8 || unroll == 16 ||
+                  unroll == 32,
+              "unroll must be 0 (auto), 4, 8, or 16 or 32 (stream kernel)");
   const int tiles = (N + 15) / 16;
   auto stream = c10::hip::getCurrentHIPStream();
   if (skinny_use_persistent(persistent, tiles_per_wg != 0 || unroll != 0, M,
@@ -628,6 +864,17 @@ void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
     TORCH_CHECK(tiles_per_wg == 0 && unroll == 0,
                 "persistent=1 has no tiles_per_wg or unroll variants");
     PERSIST_LAUNCH(KUNROLL, false, tiles, 16);
+    HIP_CHECK_LAST();
+    return;
+  }
+  int snt = 1;
+  if (const int chunks = skinny_stream_chunks(unroll, tiles_per_wg, M, N, K,
+                                              tiles, x.stride(0), &snt)) {
+    const int nt = snt;
+    const int grid = (tiles + nt - 1) / nt;
+    if (chunks == 32) STREAM_LAUNCH(4, 1, grid, 16);
+    else if (nt == 2) STREAM_LAUNCH(2, 2, grid, 32);
+    else STREAM_LAUNCH(2, 1, grid, 16);
     HIP_CHECK_LAST();
     return;
   }
@@ -676,4 +923,5 @@ void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
   HIP_CHECK_LAST();
 }
 #undef SKINNY_LAUNCH
+#undef STREAM_LAUNCH
 #undef PERSIST_LAUNCH

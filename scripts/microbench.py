@@ -428,6 +428,62 @@ def persistent_probes(ext):
         del ws
 
 
+def stream_probes(ext):
+    """Stream skinny GEMM (unroll=16|32: a ring of load groups in flight per
+    wave) against the current auto dispatch on the three Llama-3-8B decode
+    projections it is meant for — o, qkv (one and two tiles per workgroup)
+    and down — at M = 1, 4, 6, 8, 16. The variants alternate in this process,
+    five rounds each; every figure is the median round and *_spread_us is
+    max - min. Weights cycle through enough copies to exceed the 256 MB
+    Infinity Cache. `auto` is the dispatcher as built (it includes the
+    stream rule once one is set); `current` pins the pre-stream choice."""
+    dev = "cuda"
+    bf16 = torch.bfloat16
+    shapes = (("o", 4096, 4096), ("qkv", 4096, 6144), ("down", 14336, 4096))
+    rounds = 5
+
+    def med(ts):
+        return round(sorted(ts)[len(ts) // 2], 1), round(max(ts) - min(ts), 1)
+
+    for name, K, N in shapes:
+        copies = max(2, min(16, (1 << 30) // (N * K * 2) + 1))
+        ws = [torch.randn(N, K, dtype=bf16, device=dev) for _ in range(copies)]
+        for M in (1, 4, 6, 8, 16):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            out = torch.empty(M, N, dtype=bf16, device=dev)
+            # what the dispatcher chose before the stream kernel existed
+            nt = 2 if (name == "qkv" and M >= 8) else 1
+            ku = 8 if K >= 8192 else 4
+
+            def call(**pins):
+                return lambda i: ext.gemm_skinny_bf16(out, x, ws[i], **pins)
+
+            fns = {
+                "current": call(tiles_per_wg=nt, unroll=ku),
+                "auto": call(),
+                "stream16": call(tiles_per_wg=1, unroll=16),
+                "stream32": call(tiles_per_wg=1, unroll=32),
+            }
+            if name == "qkv":
+                fns["stream16_nt2"] = call(tiles_per_wg=2, unroll=16)
+            ts = {k: [] for k in fns}
+            for _ in range(rounds):
+                for k, fn in fns.items():
+                    ts[k].append(_time_us(fn, copies, iters=200, reps=1))
+            rec = {"probe": f"skinny_stream_{name}_M{M}_K{K}_N{N}",
+                   "copies": copies, "current_nt": nt, "current_unroll": ku}
+            for k in fns:
+                rec[f"{k}_us"], rec[f"{k}_spread_us"] = med(ts[k])
+            best = min((k for k in fns if k.startswith("stream")),
+                       key=lambda k: rec[f"{k}_us"])
+            rec["best_stream"] = best
+            rec["best_stream_TBps"] = round(
+                N * K * 2 / rec[f"{best}_us"] / 1e6, 2)
+            rec["current_TBps"] = round(N * K * 2 / rec["current_us"] / 1e6, 2)
+            print(json.dumps(rec), flush=True)
+        del ws
+
+
 def persistent_pmc_target(ext, which):
     """The target of a counter run: the Llama-3-8B gate_up at M=8, plain and
     fused SwiGLU, four calls each on four different weights, with the
@@ -454,6 +510,11 @@ def main():
         persistent_pmc_target(
             _hip_ext_loader.load(), sys.argv[sys.argv.index("--persistent-pmc") + 1]
         )
+        return
+    if "--stream-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        stream_probes(_hip_ext_loader.load())
         return
     if "--persistent-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
