@@ -3,13 +3,17 @@
 Attention path is identical to Llama (shared code path, paged KV); the MLP
 is a top-k routed mixture of SwiGLU experts. Expert compute is a grouped
 GEMM: tokens are sorted by expert and each expert's slice runs one bf16
-GEMM (hipBLASLt); EP over RCCL all-to-all is the round-2 extension — with
+GEMM (hipBLASLt). On a single rank, steps with T * top_k <= 64 run the
+grouped skinny kernel and the step sizes measured to win (MoEMLP.tiled,
+ops.moe_tiled_rule) the tiled grouped GEMM, both with routing on device and
+no stream sync; EP over RCCL all-to-all is the round-2 extension — with
 tp.size>1 experts are sharded over ranks and the combine is the existing
 row-parallel all-reduce.
 """
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -50,6 +54,11 @@ class MoEMLP(nn.Module):
             torch.empty(self.experts_local, self.hidden, self.inter, dtype=dtype),
             requires_grad=False,
         )
+        # steps with T * top_k > 64 on a single rank: None = the measured
+        # rule (ops.moe_tiled_rule), True = always the tiled grouped GEMM,
+        # False = always the per-expert loop
+        pin = os.environ.get("DTS_MOE_TILED")
+        self.tiled: Optional[bool] = None if pin is None else pin == "1"
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         T = x.shape[0]
@@ -73,6 +82,16 @@ class MoEMLP(nn.Module):
             return self._forward_grouped(
                 x, flat_tok, flat_expert, weights, T
             )
+        if x.is_cuda and ops.hip_available():
+            tiled = self.tiled
+            if tiled is None:
+                tiled = ops.moe_tiled_rule(
+                    self.hidden, self.inter, T * self.top_k
+                )
+            if tiled:
+                return self._forward_tiled(
+                    x, flat_tok, flat_expert, weights, T
+                )
 
         out = torch.zeros(T, self.hidden, dtype=torch.float32, device=x.device)
         # prefill path: one GEMM per locally-resident expert slice.
@@ -88,9 +107,10 @@ class MoEMLP(nn.Module):
             out.index_add_(0, toks, ye.float() * flat_w[sel].unsqueeze(1).float())
         return out.to(x.dtype)
 
-    def _forward_grouped(self, x, flat_tok, flat_expert, weights, T):
-        """Decode MoE via the grouped per-expert MFMA GEMM: every shape
-        is static in T*k, all routing state stays on device."""
+    def _route_sorted(self, x, flat_tok, flat_expert):
+        """Routing prologue of the grouped paths, all on device: rows of x
+        gathered in expert order, per-expert counts and offsets, and the
+        inverse permutation back to (token, k) order."""
         P = flat_tok.shape[0]
         order = torch.argsort(flat_expert, stable=True)
         inv = torch.empty_like(order)
@@ -108,13 +128,37 @@ class MoEMLP(nn.Module):
         )
         offsets = (torch.cumsum(counts, 0) - counts).to(torch.int32)
         x_sorted = x.index_select(0, flat_tok.index_select(0, order))
+        return x_sorted, counts, offsets, inv
+
+    def _combine(self, y, inv, weights, T, dtype):
+        y = y.index_select(0, inv).view(T, self.top_k, self.hidden)
+        out = (y.float() * weights.unsqueeze(-1).float()).sum(dim=1)
+        return out.to(dtype)
+
+    def _forward_grouped(self, x, flat_tok, flat_expert, weights, T):
+        """Decode MoE via the grouped per-expert MFMA GEMM: every shape
+        is static in T*k, all routing state stays on device."""
+        x_sorted, counts, offsets, inv = self._route_sorted(
+            x, flat_tok, flat_expert
+        )
         gu = ops.moe_grouped_linear(x_sorted, self.gate_up_w, counts, offsets)
         y = ops.moe_grouped_linear(
             ops.silu_mul(gu), self.down_w, counts, offsets
         )
-        y = y.index_select(0, inv).view(T, self.top_k, self.hidden)
-        out = (y.float() * weights.unsqueeze(-1).float()).sum(dim=1)
-        return out.to(x.dtype)
+        return self._combine(y, inv, weights, T, x.dtype)
+
+    def _forward_tiled(self, x, flat_tok, flat_expert, weights, T):
+        """Steps past the decode sizes via the tiled grouped GEMM: the
+        same prologue and combine, SwiGLU fused into the gate_up GEMM.
+        Nothing here syncs the stream."""
+        x_sorted, counts, offsets, inv = self._route_sorted(
+            x, flat_tok, flat_expert
+        )
+        act = ops.moe_grouped_gemm(
+            x_sorted, self.gate_up_w, counts, offsets, swiglu=True
+        )
+        y = ops.moe_grouped_gemm(act, self.down_w, counts, offsets)
+        return self._combine(y, inv, weights, T, x.dtype)
 
     def _forward_ep(self, x, flat_tok, flat_expert, flat_w) -> torch.Tensor:
         """Expert-parallel dispatch: ship each (token, expert) assignment

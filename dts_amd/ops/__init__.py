@@ -319,6 +319,38 @@ def moe_grouped_linear(x, w, counts, offsets):
     return torch_ref.moe_grouped_linear(x, w, counts, offsets)
 
 
+def moe_grouped_gemm(x, w, counts, offsets, swiglu=False):
+    """Tiled grouped per-expert GEMM for steps past the decode sizes: the
+    same contract as moe_grouped_linear (device-side counts/offsets, rows
+    sorted by expert), 64-row blocks so an expert's weights stream once per
+    64 rows of its segment. swiglu: w = [E, 2I, K] = [gate; up] and the
+    result is [P, I] = silu_mul of the plain result. Rows that no segment
+    owns are left unwritten on the GPU."""
+    if _on_gpu(x):
+        ext = _require_hip()
+        if ext is not None:
+            n = w.shape[1] // 2 if swiglu else w.shape[1]
+            out = torch.empty((x.shape[0], n), dtype=x.dtype, device=x.device)
+            ext.moe_grouped_gemm(out, x, w, counts, offsets, swiglu)
+            return out
+    out = torch_ref.moe_grouped_linear(x, w, counts, offsets)
+    return silu_mul(out) if swiglu else out
+
+
+# (hidden, intermediate) -> (lo, hi): MoEMLP takes the tiled grouped GEMM for
+# lo <= T * top_k <= hi. Only ranges measured to win by more than 3x the
+# larger spread for both routings are listed (docs/KERNELS.md, "Tiled grouped
+# MoE GEMM"); shapes that were not timed stay on the per-expert loop.
+# Mixtral-8x7B: wins from 66 rows (1770 -> 644 us) to 1024 (1978 -> 1414 us,
+# skewed); at 2048 rows the skewed routing is a tie and beyond it loses.
+_MOE_TILED_RANGES: dict = {(4096, 14336): (66, 1024)}
+
+
+def moe_tiled_rule(hidden: int, inter: int, rows: int) -> bool:
+    lo, hi = _MOE_TILED_RANGES.get((hidden, inter), (1, 0))
+    return lo <= rows <= hi
+
+
 def linear_bf16(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     """y = x @ W^T. Skinny decode batches (M<=16, bf16, K%512==0) stream
     through custom weight-streaming kernels; everything else is a

@@ -53,6 +53,9 @@ void gemm_skinny_swiglu_bf16(torch::Tensor out, torch::Tensor x,
 int64_t skinny_persistent_pin(int64_t pin);
 void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                         torch::Tensor counts, torch::Tensor offsets);
+void moe_grouped_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                      torch::Tensor counts, torch::Tensor offsets,
+                      bool swiglu);
 void gemm_skinny_w8_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w_q,
                          torch::Tensor scale, int64_t tiles_per_wg,
                          int64_t unroll);
@@ -133,6 +136,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pin"));
   m.def("moe_grouped_linear", &moe_grouped_linear,
         "grouped per-expert skinny GEMM (capture-safe MoE decode)");
+  m.def("moe_grouped_gemm", &moe_grouped_gemm,
+        "tiled grouped per-expert GEMM: out[p] = x[p] @ w[e]^T for the rows "
+        "of expert e's segment [offsets[e], offsets[e] + counts[e]) (int32 "
+        "device tensors, E <= 64, K % 64 == 0); rows of no segment are not "
+        "written. swiglu: w = [E, 2I, K] = [gate; up], I % 16 == 0, out = "
+        "[P, I] = silu_mul of the plain result",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("counts"),
+        py::arg("offsets"), py::arg("swiglu") = false);
   m.def("gemm_skinny_w8_bf16", &gemm_skinny_w8_bf16,
         "W8A16 skinny-M (M<=16) GEMM: FP8 e4m3fn weights [N,K] with an fp32 "
         "per-row scale [N], bf16 x/out, fp32 accumulation; tiles_per_wg and "

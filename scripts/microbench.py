@@ -484,6 +484,101 @@ def stream_probes(ext):
         del ws
 
 
+def moe_tiled_probes(ext):
+    """Tiled grouped MoE GEMM against the per-expert loop at one Mixtral-8x7B
+    layer (E = 8, H = 4096, I = 14336, top_k = 2; 2.8 GB of experts, far past
+    the Infinity Cache, so weights are cold without cycling). Per T and
+    routing (near-uniform; skewed = half the assignments on two experts) it
+    times the whole MoEMLP.forward with `tiled` False and True, and the two
+    GEMM calls alone (moe_grouped_gemm with fused SwiGLU, then down) against
+    F.linear + silu_mul + F.linear per expert on host-known segments. The
+    variants alternate in this process, five rounds; every figure is the
+    median round and *_spread_us is max - min."""
+    import torch.nn.functional as F
+
+    from dts_amd import ops
+    from dts_amd.models.config import ModelSpec
+    from dts_amd.models.mixtral import MoEMLP
+    from dts_amd.parallel.tp import TPContext
+
+    E, H, I, TOP_K = 8, 4096, 14336, 2
+    spec = ModelSpec(
+        name="moe-bench", arch="mixtral", vocab_size=512, hidden_size=H,
+        intermediate_size=I, num_layers=1, num_heads=32, num_kv_heads=8,
+        head_dim=128, rope_theta=1e4, max_position=2048,
+        num_experts=E, experts_per_token=TOP_K,
+    )
+    moe = MoEMLP(spec, TPContext.single(), torch.bfloat16).to("cuda")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    with torch.no_grad():
+        moe.gate_up_w.normal_(0, 0.02, generator=g)
+        moe.down_w.normal_(0, 0.02, generator=g)
+        # expert e's logit is 4 x[:, e]: the first E columns of x pick the
+        # experts, the other columns are ordinary activations
+        moe.router_w.zero_()
+        moe.router_w[:, :E] = 4.0 * torch.eye(E, device="cuda")
+
+    def routed_x(T, skewed):
+        t = torch.arange(T)
+        if skewed:  # tokens 0, 2, 4, ... take experts (0, 1)
+            rest = t // 2
+            e1 = torch.where(t % 2 == 0, 0, 2 + rest % 6)
+            e2 = torch.where(t % 2 == 0, 1, 2 + (rest + 1 + (rest // 6) % 5) % 6)
+        else:
+            e1 = t % E
+            e2 = (t + 1 + (t // E) % (E - 1)) % E
+        x = torch.randn(T, H, generator=torch.Generator().manual_seed(T))
+        x[:, :E] = 0.0
+        x[t, e1], x[t, e2] = 4.0, 3.5
+        return x.to(torch.bfloat16).cuda(), torch.bincount(
+            torch.cat([e1, e2]), minlength=E).tolist()
+
+    def med(ts):
+        return round(sorted(ts)[len(ts) // 2], 1), round(max(ts) - min(ts), 1)
+
+    for T in (33, 64, 128, 256, 512, 1024, 2048, 4096):
+        for routing in ("uniform", "skewed"):
+            x, hist = routed_x(T, routing == "skewed")
+            counts = torch.tensor(hist, dtype=torch.int32, device="cuda")
+            offsets = (torch.cumsum(counts, 0) - counts).to(torch.int32)
+            segs = [(int(o), int(o) + c) for o, c in zip(offsets.tolist(), hist)]
+            xs = torch.randn(T * TOP_K, H, dtype=torch.bfloat16, device="cuda")
+
+            def forward(tiled):
+                def fn(_):
+                    moe.tiled = tiled
+                    with torch.inference_mode():
+                        moe(x)
+                return fn
+
+            def gemms_tiled(_):
+                act = ops.moe_grouped_gemm(xs, moe.gate_up_w, counts, offsets, True)
+                ops.moe_grouped_gemm(act, moe.down_w, counts, offsets)
+
+            def gemms_linear(_):
+                for e, (a, b) in enumerate(segs):
+                    F.linear(ops.silu_mul(F.linear(xs[a:b], moe.gate_up_w[e])),
+                             moe.down_w[e])
+
+            fns = {"loop": forward(False), "tiled": forward(True),
+                   "gemms_linear": gemms_linear, "gemms_tiled": gemms_tiled}
+            with torch.inference_mode():
+                moe.tiled = True
+                assert moe(x).isfinite().all()
+            iters = 20 if T <= 512 else 8
+            ts = {k: [] for k in fns}
+            for _ in range(5):
+                for k, fn in fns.items():
+                    ts[k].append(_time_us(fn, 1, iters=iters, reps=1))
+            rec = {"probe": f"moe_tiled_T{T}_{routing}", "rows": T * TOP_K,
+                   "K": H, "N": I, "hist": hist}
+            for k in fns:
+                rec[f"{k}_us"], rec[f"{k}_spread_us"] = med(ts[k])
+            spread = max(rec["loop_spread_us"], rec["tiled_spread_us"])
+            rec["tiled_wins"] = rec["loop_us"] - rec["tiled_us"] > 3 * spread
+            print(json.dumps(rec), flush=True)
+
+
 def persistent_pmc_target(ext, which):
     """The target of a counter run: the Llama-3-8B gate_up at M=8, plain and
     fused SwiGLU, four calls each on four different weights, with the
@@ -510,6 +605,11 @@ def main():
         persistent_pmc_target(
             _hip_ext_loader.load(), sys.argv[sys.argv.index("--persistent-pmc") + 1]
         )
+        return
+    if "--moe-tiled-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        moe_tiled_probes(_hip_ext_loader.load())
         return
     if "--stream-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
