@@ -6,7 +6,8 @@ GEMM: tokens are sorted by expert and each expert's slice runs one bf16
 GEMM (hipBLASLt). On a single rank, steps with T * top_k <= 64 run the
 grouped skinny kernel and the step sizes measured to win (MoEMLP.tiled,
 ops.moe_tiled_rule) the tiled grouped GEMM, both with routing on device and
-no stream sync; EP over RCCL all-to-all is the round-2 extension — with
+no stream sync (with MoEMLP.fused_route the router, the expert sort and the
+combine around them are three HIP kernels too); EP over RCCL all-to-all is the round-2 extension — with
 tp.size>1 experts are sharded over ranks and the combine is the existing
 row-parallel all-reduce.
 """
@@ -23,6 +24,7 @@ import torch.nn.functional as F
 from dts_amd import ops
 from dts_amd.models.config import ModelSpec
 from dts_amd.models.llama import LlamaAttention
+from dts_amd.ops import torch_ref
 from dts_amd.ops.torch_ref import build_rope_cache
 from dts_amd.parallel.tp import TPContext, _init_weight
 from dts_amd.serving.batch import ForwardBatch
@@ -59,12 +61,32 @@ class MoEMLP(nn.Module):
         # False = always the per-expert loop
         pin = os.environ.get("DTS_MOE_TILED")
         self.tiled: Optional[bool] = None if pin is None else pin == "1"
+        # single-rank GPU steps of the two grouped paths: route, sort and
+        # combine in the fused HIP kernels (ops.moe_route, moe_sort_gather,
+        # moe_combine) instead of the torch chain. Off by default: the fused
+        # router sums a logit in another order, so a near-tie can pick
+        # another expert
+        self.fused_route: bool = os.environ.get("DTS_MOE_FUSED_ROUTE") == "1"
+
+    def _grouped_path(self, x: torch.Tensor) -> Optional[str]:
+        """Which grouped GEMM path a single-rank step takes: "grouped",
+        "tiled" or None (the per-expert loop)."""
+        if not (x.is_cuda and ops.hip_available()):
+            return None
+        rows = x.shape[0] * self.top_k
+        if rows <= 64:
+            return "grouped"
+        tiled = self.tiled
+        if tiled is None:
+            tiled = ops.moe_tiled_rule(self.hidden, self.inter, rows)
+        return "tiled" if tiled else None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         T = x.shape[0]
-        logits = F.linear(x.float(), self.router_w.float())  # [T, E]
-        weights, experts = torch.topk(torch.softmax(logits, dim=-1), self.top_k)
-        weights = weights / weights.sum(dim=-1, keepdim=True)
+        path = self._grouped_path(x) if self.tp.size == 1 else None
+        if self.fused_route and path is not None:
+            return self._forward_fused(x, path == "tiled")
+        weights, experts = torch_ref.moe_route(x, self.router_w, self.top_k)
 
         flat_expert = experts.reshape(-1)  # [T*k]
         flat_tok = (
@@ -74,7 +96,7 @@ class MoEMLP(nn.Module):
         if self.tp.size > 1:
             return self._forward_ep(x, flat_tok, flat_expert, flat_w)
 
-        if x.is_cuda and T * self.top_k <= 64 and ops.hip_available():
+        if path == "grouped":
             # capture-safe decode path: sort assignments by expert on
             # device and run the grouped skinny GEMM with device-side
             # counts — no nonzero()/masked gather, so the whole step is
@@ -82,16 +104,8 @@ class MoEMLP(nn.Module):
             return self._forward_grouped(
                 x, flat_tok, flat_expert, weights, T
             )
-        if x.is_cuda and ops.hip_available():
-            tiled = self.tiled
-            if tiled is None:
-                tiled = ops.moe_tiled_rule(
-                    self.hidden, self.inter, T * self.top_k
-                )
-            if tiled:
-                return self._forward_tiled(
-                    x, flat_tok, flat_expert, weights, T
-                )
+        if path == "tiled":
+            return self._forward_tiled(x, flat_tok, flat_expert, weights, T)
 
         out = torch.zeros(T, self.hidden, dtype=torch.float32, device=x.device)
         # prefill path: one GEMM per locally-resident expert slice.
@@ -107,58 +121,51 @@ class MoEMLP(nn.Module):
             out.index_add_(0, toks, ye.float() * flat_w[sel].unsqueeze(1).float())
         return out.to(x.dtype)
 
-    def _route_sorted(self, x, flat_tok, flat_expert):
-        """Routing prologue of the grouped paths, all on device: rows of x
-        gathered in expert order, per-expert counts and offsets, and the
-        inverse permutation back to (token, k) order."""
-        P = flat_tok.shape[0]
-        order = torch.argsort(flat_expert, stable=True)
-        inv = torch.empty_like(order)
-        inv.scatter_(
-            0, order, torch.arange(P, device=x.device, dtype=order.dtype)
+    def _forward_fused(self, x, tiled: bool):
+        """Both grouped paths with routing, expert sort and combine in the
+        fused kernels: five launches (six on the skinny path), no sync."""
+        weights, experts = ops.moe_route(x, self.router_w, self.top_k)
+        x_sorted, counts, offsets, dst = ops.moe_sort_gather(
+            x, experts, self.num_experts
         )
-        # capture-safe histogram: torch.bincount syncs the stream
-        # internally (aborted hipGraph capture mid-bench; caught by
-        # test_grouped_path_is_capture_safe) — index_add_ does not
-        counts = torch.zeros(
-            self.num_experts, dtype=torch.int32, device=x.device
-        )
-        counts.index_add_(
-            0, flat_expert, torch.ones_like(flat_expert, dtype=torch.int32)
-        )
-        offsets = (torch.cumsum(counts, 0) - counts).to(torch.int32)
-        x_sorted = x.index_select(0, flat_tok.index_select(0, order))
-        return x_sorted, counts, offsets, inv
-
-    def _combine(self, y, inv, weights, T, dtype):
-        y = y.index_select(0, inv).view(T, self.top_k, self.hidden)
-        out = (y.float() * weights.unsqueeze(-1).float()).sum(dim=1)
-        return out.to(dtype)
+        if tiled:
+            act = ops.moe_grouped_gemm(
+                x_sorted, self.gate_up_w, counts, offsets, swiglu=True
+            )
+            y = ops.moe_grouped_gemm(act, self.down_w, counts, offsets)
+        else:
+            gu = ops.moe_grouped_linear(
+                x_sorted, self.gate_up_w, counts, offsets
+            )
+            y = ops.moe_grouped_linear(
+                ops.silu_mul(gu), self.down_w, counts, offsets
+            )
+        return ops.moe_combine(y, dst, weights)
 
     def _forward_grouped(self, x, flat_tok, flat_expert, weights, T):
         """Decode MoE via the grouped per-expert MFMA GEMM: every shape
         is static in T*k, all routing state stays on device."""
-        x_sorted, counts, offsets, inv = self._route_sorted(
-            x, flat_tok, flat_expert
+        x_sorted, counts, offsets, inv = torch_ref.moe_sort_gather(
+            x, flat_tok, flat_expert, self.num_experts
         )
         gu = ops.moe_grouped_linear(x_sorted, self.gate_up_w, counts, offsets)
         y = ops.moe_grouped_linear(
             ops.silu_mul(gu), self.down_w, counts, offsets
         )
-        return self._combine(y, inv, weights, T, x.dtype)
+        return torch_ref.moe_combine(y, inv, weights)
 
     def _forward_tiled(self, x, flat_tok, flat_expert, weights, T):
         """Steps past the decode sizes via the tiled grouped GEMM: the
         same prologue and combine, SwiGLU fused into the gate_up GEMM.
         Nothing here syncs the stream."""
-        x_sorted, counts, offsets, inv = self._route_sorted(
-            x, flat_tok, flat_expert
+        x_sorted, counts, offsets, inv = torch_ref.moe_sort_gather(
+            x, flat_tok, flat_expert, self.num_experts
         )
         act = ops.moe_grouped_gemm(
             x_sorted, self.gate_up_w, counts, offsets, swiglu=True
         )
         y = ops.moe_grouped_gemm(act, self.down_w, counts, offsets)
-        return self._combine(y, inv, weights, T, x.dtype)
+        return torch_ref.moe_combine(y, inv, weights)
 
     def _forward_ep(self, x, flat_tok, flat_expert, flat_w) -> torch.Tensor:
         """Expert-parallel dispatch: ship each (token, expert) assignment

@@ -337,6 +337,60 @@ def moe_grouped_gemm(x, w, counts, offsets, swiglu=False):
     return silu_mul(out) if swiglu else out
 
 
+def moe_route(x, router_w, top_k):
+    """MoE router for x [T, H]: softmax over the experts' fp32 logits, top-k
+    with the lowest index first on ties, weights renormalised over the picked
+    experts. Returns (weights fp32 [T, k], experts [T, k]; int32 from the
+    HIP kernel). The kernel sums a logit in another order than the reference's
+    F.linear, so weights agree in all but their last bits."""
+    if _on_gpu(x):
+        ext = _require_hip()
+        if ext is not None:
+            T = x.shape[0]
+            experts = torch.empty((T, top_k), dtype=torch.int32, device=x.device)
+            weights = torch.empty((T, top_k), dtype=torch.float32, device=x.device)
+            ext.moe_route(experts, weights, x, router_w)
+            return weights, experts
+    return torch_ref.moe_route(x, router_w, top_k)
+
+
+def moe_sort_gather(x, experts, num_experts):
+    """Stable sort of the T * k assignments (p = t * k + j, expert
+    experts[t, j]) by expert. Returns (x_sorted [P, H] = x's rows in sorted
+    order, counts [E], offsets [E] = the experts' segments for the grouped
+    GEMMs, dst [P] = the sorted row of assignment p). All on device and
+    integer-exact; the HIP kernel clamps expert ids to [0, E - 1]."""
+    T, k = experts.shape
+    if _on_gpu(x):
+        ext = _require_hip()
+        if ext is not None:
+            dev = x.device
+            x_sorted = torch.empty((T * k, x.shape[1]), dtype=x.dtype, device=dev)
+            dst = torch.empty(T * k, dtype=torch.int32, device=dev)
+            counts = torch.empty(num_experts, dtype=torch.int32, device=dev)
+            offsets = torch.empty(num_experts, dtype=torch.int32, device=dev)
+            ext.moe_sort_gather(x_sorted, dst, counts, offsets, x, experts)
+            return x_sorted, counts, offsets, dst
+    flat_tok = torch.arange(T, device=x.device).unsqueeze(1).expand(T, k).reshape(-1)
+    return torch_ref.moe_sort_gather(
+        x, flat_tok, experts.reshape(-1).long(), num_experts
+    )
+
+
+def moe_combine(y, dst, weights):
+    """out[t] = sum_j weights[t, j] * y[dst[t * k + j]] in fp32, ascending j,
+    rounded once to y's dtype: the grouped GEMMs' rows back in token order."""
+    if _on_gpu(y):
+        ext = _require_hip()
+        if ext is not None:
+            out = torch.empty(
+                (weights.shape[0], y.shape[1]), dtype=y.dtype, device=y.device
+            )
+            ext.moe_combine(out, y, dst, weights)
+            return out
+    return torch_ref.moe_combine(y, dst.long(), weights)
+
+
 # (hidden, intermediate) -> (lo, hi): MoEMLP takes the tiled grouped GEMM for
 # lo <= T * top_k <= hi. Only ranges measured to win by more than 3x the
 # larger spread for both routings are listed (docs/KERNELS.md, "Tiled grouped

@@ -56,6 +56,13 @@ void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 void moe_grouped_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                       torch::Tensor counts, torch::Tensor offsets,
                       bool swiglu);
+void moe_route(torch::Tensor experts_out, torch::Tensor weights_out,
+               torch::Tensor x, torch::Tensor router_w);
+void moe_sort_gather(torch::Tensor x_sorted, torch::Tensor dst,
+                     torch::Tensor counts, torch::Tensor offsets,
+                     torch::Tensor x, torch::Tensor experts);
+void moe_combine(torch::Tensor out, torch::Tensor y, torch::Tensor dst,
+                 torch::Tensor weights);
 void gemm_skinny_w8_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w_q,
                          torch::Tensor scale, int64_t tiles_per_wg,
                          int64_t unroll);
@@ -144,6 +151,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[P, I] = silu_mul of the plain result",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("counts"),
         py::arg("offsets"), py::arg("swiglu") = false);
+  m.def("moe_route", &moe_route,
+        "MoE router: fp32 logits x @ router_w^T, softmax over the E <= 64 "
+        "experts, top-k (k = experts_out.size(1) <= min(E, 8), lowest index "
+        "on ties) into experts_out int32 [T, k], renormalised weights into "
+        "weights_out fp32 [T, k]; x bf16 [T, H], H % 8 == 0",
+        py::arg("experts_out"), py::arg("weights_out"), py::arg("x"),
+        py::arg("router_w"));
+  m.def("moe_sort_gather", &moe_sort_gather,
+        "stable sort of the T * k assignments by expert: dst[p] is the "
+        "sorted row of assignment p = t * k + j, x_sorted[dst[p]] = x[t], "
+        "counts / offsets int32 [E] are the expert segments; expert ids are "
+        "clamped to [0, E - 1]",
+        py::arg("x_sorted"), py::arg("dst"), py::arg("counts"),
+        py::arg("offsets"), py::arg("x"), py::arg("experts"));
+  m.def("moe_combine", &moe_combine,
+        "out[t] = bf16(sum_j weights[t, j] * float(y[dst[t * k + j]])), "
+        "ascending j, products and sums rounded to fp32",
+        py::arg("out"), py::arg("y"), py::arg("dst"), py::arg("weights"));
   m.def("gemm_skinny_w8_bf16", &gemm_skinny_w8_bf16,
         "W8A16 skinny-M (M<=16) GEMM: FP8 e4m3fn weights [N,K] with an fp32 "
         "per-row scale [N], bf16 x/out, fp32 accumulation; tiles_per_wg and "

@@ -335,6 +335,54 @@ def moe_grouped_linear(
     return out
 
 
+def moe_route(x: torch.Tensor, router_w: torch.Tensor, top_k: int):
+    """MoE router: fp32 logits, softmax over all experts, top-k, weights
+    renormalised over the picked experts. Returns (weights fp32 [T, k],
+    experts [T, k])."""
+    logits = torch.nn.functional.linear(x.float(), router_w.float())  # [T, E]
+    weights, experts = torch.topk(torch.softmax(logits, dim=-1), top_k)
+    weights = weights / weights.sum(dim=-1, keepdim=True)
+    return weights, experts
+
+
+def moe_sort_gather(
+    x: torch.Tensor,  # [T, H]
+    flat_tok: torch.Tensor,  # [P] token of each assignment
+    flat_expert: torch.Tensor,  # [P] expert of each assignment
+    num_experts: int,
+):
+    """Routing prologue of the grouped paths, all on device: rows of x
+    gathered in expert order, per-expert counts and offsets, and the
+    inverse permutation back to (token, k) order."""
+    P = flat_tok.shape[0]
+    order = torch.argsort(flat_expert, stable=True)
+    inv = torch.empty_like(order)
+    inv.scatter_(0, order, torch.arange(P, device=x.device, dtype=order.dtype))
+    # capture-safe histogram: torch.bincount syncs the stream
+    # internally (aborted hipGraph capture mid-bench; caught by
+    # test_grouped_path_is_capture_safe) — index_add_ does not
+    counts = torch.zeros(num_experts, dtype=torch.int32, device=x.device)
+    counts.index_add_(
+        0, flat_expert, torch.ones_like(flat_expert, dtype=torch.int32)
+    )
+    offsets = (torch.cumsum(counts, 0) - counts).to(torch.int32)
+    x_sorted = x.index_select(0, flat_tok.index_select(0, order))
+    return x_sorted, counts, offsets, inv
+
+
+def moe_combine(
+    y: torch.Tensor,  # [P, H] expert outputs in sorted order
+    inv: torch.Tensor,  # [P] sorted row of assignment t * k + j
+    weights: torch.Tensor,  # [T, k]
+) -> torch.Tensor:
+    """Inverse-permute weighted sum back in token order, fp32, one rounding
+    to y's dtype."""
+    T, k = weights.shape
+    y = y.index_select(0, inv).view(T, k, y.shape[1])
+    out = (y.float() * weights.unsqueeze(-1).float()).sum(dim=1)
+    return out.to(y.dtype)
+
+
 def top_k_active(top_k: int, V: int) -> bool:
     """top-k filters for 1 <= top_k < V; 0 and >= V disable it."""
     return 1 <= top_k < V

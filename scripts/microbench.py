@@ -579,6 +579,90 @@ def moe_tiled_probes(ext):
             print(json.dumps(rec), flush=True)
 
 
+def moe_route_probes(ext):
+    """Fused MoE routing glue (MoEMLP.fused_route: moe_route, moe_sort_gather,
+    moe_combine) against the torch chain at one Mixtral-8x7B layer (E = 8,
+    H = 4096, I = 14336, top_k = 2), near-uniform routing. Per T the whole
+    MoEMLP.forward is timed with the flag off and on, eager and as a captured
+    graph that is replayed; T <= 32 runs the grouped skinny GEMM, above that
+    the tiled grouped GEMM (ops.moe_tiled_rule). The four variants alternate
+    in this process, five rounds; every figure is the median round and
+    *_spread_us is max - min. The router's logits are 16, 14 and 0, so both
+    routers pick the same experts; `bit_equal` says whether the two outputs
+    are the same bits."""
+    from dts_amd.models.config import ModelSpec
+    from dts_amd.models.mixtral import MoEMLP
+    from dts_amd.parallel.tp import TPContext
+
+    E, H, I, TOP_K = 8, 4096, 14336, 2
+    spec = ModelSpec(
+        name="moe-bench", arch="mixtral", vocab_size=512, hidden_size=H,
+        intermediate_size=I, num_layers=1, num_heads=32, num_kv_heads=8,
+        head_dim=128, rope_theta=1e4, max_position=2048,
+        num_experts=E, experts_per_token=TOP_K,
+    )
+    moe = MoEMLP(spec, TPContext.single(), torch.bfloat16).to("cuda")
+    moe.tiled = None
+    g = torch.Generator(device="cuda").manual_seed(0)
+    with torch.no_grad():
+        moe.gate_up_w.normal_(0, 0.02, generator=g)
+        moe.down_w.normal_(0, 0.02, generator=g)
+        moe.router_w.zero_()
+        moe.router_w[:, :E] = 4.0 * torch.eye(E, device="cuda")
+
+    def med(ts):
+        return round(sorted(ts)[len(ts) // 2], 1), round(max(ts) - min(ts), 1)
+
+    for T in (1, 6, 16, 33, 128, 512):
+        t = torch.arange(T)
+        x = torch.randn(T, H, generator=torch.Generator().manual_seed(T))
+        x[:, :E] = 0.0
+        x[t, t % E], x[t, (t + 1 + (t // E) % (E - 1)) % E] = 4.0, 3.5
+        x = x.to(torch.bfloat16).cuda()
+
+        fns, outs = {}, {}
+        for name, fused in (("torch", False), ("fused", True)):
+            def eager(_, fused=fused):
+                moe.fused_route = fused
+                with torch.inference_mode():
+                    return moe(x)
+
+            moe.fused_route = fused
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), torch.inference_mode():
+                for _ in range(2):
+                    moe(x)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.inference_mode(), torch.cuda.graph(graph):
+                outs[f"graph_{name}"] = moe(x)
+            outs[f"eager_{name}"] = eager(0)
+            fns[f"eager_{name}"] = eager
+            fns[f"graph_{name}"] = lambda _, graph=graph: graph.replay()
+        for fn in fns.values():
+            fn(0)
+        torch.cuda.synchronize()
+        ts = {k: [] for k in fns}
+        for _ in range(5):
+            for k, fn in fns.items():
+                ts[k].append(_time_us(fn, 1, iters=50, reps=1))
+        rec = {"probe": f"moe_route_T{T}", "rows": T * TOP_K,
+               "path": "grouped" if T * TOP_K <= 64 else "tiled"}
+        for k in fns:
+            rec[f"{k}_us"], rec[f"{k}_spread_us"] = med(ts[k])
+        for mode in ("eager", "graph"):
+            a, b = outs[f"{mode}_torch"], outs[f"{mode}_fused"]
+            rec[f"{mode}_bit_equal"] = bool(torch.equal(a, b))
+            spread = max(rec[f"{mode}_torch_spread_us"], rec[f"{mode}_fused_spread_us"])
+            rec[f"{mode}_fused_wins"] = (
+                rec[f"{mode}_torch_us"] - rec[f"{mode}_fused_us"] > 3 * spread
+            )
+        print(json.dumps(rec), flush=True)
+    moe.fused_route = False
+
+
 def persistent_pmc_target(ext, which):
     """The target of a counter run: the Llama-3-8B gate_up at M=8, plain and
     fused SwiGLU, four calls each on four different weights, with the
@@ -610,6 +694,11 @@ def main():
         from dts_amd.ops import _hip_ext_loader
 
         moe_tiled_probes(_hip_ext_loader.load())
+        return
+    if "--moe-route-only" in sys.argv:
+        from dts_amd.ops import _hip_ext_loader
+
+        moe_route_probes(_hip_ext_loader.load())
         return
     if "--stream-only" in sys.argv:
         from dts_amd.ops import _hip_ext_loader
