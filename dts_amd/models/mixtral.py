@@ -61,6 +61,9 @@ class MoEMLP(nn.Module):
         # False = always the per-expert loop
         pin = os.environ.get("DTS_MOE_TILED")
         self.tiled: Optional[bool] = None if pin is None else pin == "1"
+        # rows per block of the tiled grouped GEMM: 0 = the kernel's own
+        # choice, 64 / 128 = pinned (ops.moe_grouped_gemm; the same bits)
+        self.tiled_block: int = int(os.environ.get("DTS_MOE_TILED_BLOCK", "0"))
         # single-rank GPU steps of the two grouped paths: route, sort and
         # combine in the fused HIP kernels (ops.moe_route, moe_sort_gather,
         # moe_combine) instead of the torch chain. Off by default: the fused
@@ -130,9 +133,12 @@ class MoEMLP(nn.Module):
         )
         if tiled:
             act = ops.moe_grouped_gemm(
-                x_sorted, self.gate_up_w, counts, offsets, swiglu=True
+                x_sorted, self.gate_up_w, counts, offsets, swiglu=True,
+                block=self.tiled_block,
             )
-            y = ops.moe_grouped_gemm(act, self.down_w, counts, offsets)
+            y = ops.moe_grouped_gemm(
+                act, self.down_w, counts, offsets, block=self.tiled_block
+            )
         else:
             gu = ops.moe_grouped_linear(
                 x_sorted, self.gate_up_w, counts, offsets
@@ -162,9 +168,12 @@ class MoEMLP(nn.Module):
             x, flat_tok, flat_expert, self.num_experts
         )
         act = ops.moe_grouped_gemm(
-            x_sorted, self.gate_up_w, counts, offsets, swiglu=True
+            x_sorted, self.gate_up_w, counts, offsets, swiglu=True,
+            block=self.tiled_block,
         )
-        y = ops.moe_grouped_gemm(act, self.down_w, counts, offsets)
+        y = ops.moe_grouped_gemm(
+            act, self.down_w, counts, offsets, block=self.tiled_block
+        )
         return torch_ref.moe_combine(y, inv, weights)
 
     def _forward_ep(self, x, flat_tok, flat_expert, flat_w) -> torch.Tensor:

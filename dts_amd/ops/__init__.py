@@ -319,19 +319,21 @@ def moe_grouped_linear(x, w, counts, offsets):
     return torch_ref.moe_grouped_linear(x, w, counts, offsets)
 
 
-def moe_grouped_gemm(x, w, counts, offsets, swiglu=False):
+def moe_grouped_gemm(x, w, counts, offsets, swiglu=False, block=0):
     """Tiled grouped per-expert GEMM for steps past the decode sizes: the
     same contract as moe_grouped_linear (device-side counts/offsets, rows
     sorted by expert), 64-row blocks so an expert's weights stream once per
     64 rows of its segment. swiglu: w = [E, 2I, K] = [gate; up] and the
     result is [P, I] = silu_mul of the plain result. Rows that no segment
-    owns are left unwritten on the GPU."""
+    owns are left unwritten on the GPU. block: 64, or 128 for the kernel
+    that shares both operands through LDS in 128-row blocks (the same bits);
+    0 = auto. The CPU path ignores it."""
     if _on_gpu(x):
         ext = _require_hip()
         if ext is not None:
             n = w.shape[1] // 2 if swiglu else w.shape[1]
             out = torch.empty((x.shape[0], n), dtype=x.dtype, device=x.device)
-            ext.moe_grouped_gemm(out, x, w, counts, offsets, swiglu)
+            ext.moe_grouped_gemm(out, x, w, counts, offsets, swiglu, block)
             return out
     out = torch_ref.moe_grouped_linear(x, w, counts, offsets)
     return silu_mul(out) if swiglu else out
@@ -396,8 +398,10 @@ def moe_combine(y, dst, weights):
 # larger spread for both routings are listed (docs/KERNELS.md, "Tiled grouped
 # MoE GEMM"); shapes that were not timed stay on the per-expert loop.
 # Mixtral-8x7B: wins from 66 rows (1770 -> 644 us) to 1024 (1978 -> 1414 us,
-# skewed); at 2048 rows the skewed routing is a tie and beyond it loses.
-_MOE_TILED_RANGES: dict = {(4096, 14336): (66, 1024)}
+# skewed) with 64-row blocks; from 1024 rows the kernel takes 128-row blocks
+# (moe_grouped_gemm's auto block) and wins to 4096 rows (2788 -> 2448 us,
+# skewed); at 8192 rows hipBLASLt's per-expert GEMMs win (3720 vs 4229 us).
+_MOE_TILED_RANGES: dict = {(4096, 14336): (66, 4096)}
 
 
 def moe_tiled_rule(hidden: int, inter: int, rows: int) -> bool:

@@ -35,6 +35,7 @@ def build(verbose: bool = True) -> Path:
         str(HIP_DIR / "gemm_skinny_fp8.hip"),
         str(HIP_DIR / "gemm_skinny_fp4.hip"),
         str(HIP_DIR / "moe_gemm.hip"),
+        str(HIP_DIR / "moe_gemm_wide.hip"),
         str(HIP_DIR / "moe_route.hip"),
     ]
     module = load(

@@ -55,7 +55,7 @@ void moe_grouped_linear(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                         torch::Tensor counts, torch::Tensor offsets);
 void moe_grouped_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                       torch::Tensor counts, torch::Tensor offsets,
-                      bool swiglu);
+                      bool swiglu, int64_t block);
 void moe_route(torch::Tensor experts_out, torch::Tensor weights_out,
                torch::Tensor x, torch::Tensor router_w);
 void moe_sort_gather(torch::Tensor x_sorted, torch::Tensor dst,
@@ -148,9 +148,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "of expert e's segment [offsets[e], offsets[e] + counts[e]) (int32 "
         "device tensors, E <= 64, K % 64 == 0); rows of no segment are not "
         "written. swiglu: w = [E, 2I, K] = [gate; up], I % 16 == 0, out = "
-        "[P, I] = silu_mul of the plain result",
+        "[P, I] = silu_mul of the plain result. block: rows per block, 64 "
+        "(weights streamed per wave) or 128 (both operands through LDS, "
+        "moe_gemm_wide_kernel), the same bits either way; 0 = auto",
         py::arg("out"), py::arg("x"), py::arg("w"), py::arg("counts"),
-        py::arg("offsets"), py::arg("swiglu") = false);
+        py::arg("offsets"), py::arg("swiglu") = false, py::arg("block") = 0);
   m.def("moe_route", &moe_route,
         "MoE router: fp32 logits x @ router_w^T, softmax over the E <= 64 "
         "experts, top-k (k = experts_out.size(1) <= min(E, 8), lowest index "

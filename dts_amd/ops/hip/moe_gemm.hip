@@ -200,9 +200,23 @@ moe_gemm_kernel(short* __restrict__ out,      // [P, N]
     }
 }
 
+// moe_gemm_wide.hip: the 128-row block kernel, same contract
+void moe_gemm_wide_launch(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                          torch::Tensor counts, torch::Tensor offsets,
+                          bool swiglu);
+
+// Rows per block that auto (block = 0) takes for a call of P rows, the only
+// size the host knows without a sync. Measured at the Mixtral-8x7B shapes
+// (docs/KERNELS.md, "128-row blocks"): from 1024 rows on the 128-row kernel
+// is faster for uniform and skewed routing alike, at 512 rows only for the
+// skewed one. Both kernels give the same bits.
+static int64_t moe_gemm_auto_block(long P) { return P >= 1024 ? 128 : MG_BM; }
+
 void moe_grouped_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                       torch::Tensor counts, torch::Tensor offsets,
-                      bool swiglu) {
+                      bool swiglu, int64_t block) {
+  TORCH_CHECK(block == 0 || block == 64 || block == 128,
+              "block must be 0 (auto), 64 or 128; got ", block);
   TORCH_CHECK(x.is_cuda() && w.is_cuda() && out.is_cuda() &&
                   counts.is_cuda() && offsets.is_cuda(),
               "moe_grouped_gemm takes device tensors");
@@ -233,6 +247,11 @@ void moe_grouped_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
               "out must be a contiguous bfloat16 [", P, ", ", N, "]; got ",
               out.sizes());
   if (P == 0) return;
+  if (block == 0) block = moe_gemm_auto_block(P);
+  if (block == 128) {
+    moe_gemm_wide_launch(out, x, w, counts, offsets, swiglu);
+    return;
+  }
   const long col_tiles = (N + MG_BN - 1) / MG_BN;
   const long grid = col_tiles * (P / MG_BM + E);
   TORCH_CHECK(P < (1L << 31) - MG_BM && grid < (1L << 31),

@@ -491,9 +491,14 @@ def moe_tiled_probes(ext):
     routing (near-uniform; skewed = half the assignments on two experts) it
     times the whole MoEMLP.forward with `tiled` False and True, and the two
     GEMM calls alone (moe_grouped_gemm with fused SwiGLU, then down) against
-    F.linear + silu_mul + F.linear per expert on host-known segments. The
+    F.linear + silu_mul + F.linear per expert on host-known segments; the
+    tiled variants run with 64-row blocks (`tiled`, `gemms_tiled`) and with
+    the 128-row LDS-shared blocks (`tiled128`, `gemms_tiled128`). The
     variants alternate in this process, five rounds; every figure is the
-    median round and *_spread_us is max - min."""
+    median round and *_spread_us is max - min. `parent` names what the rule
+    of the commit before the 128-row kernel runs at that size (`tiled` inside
+    66..1024 rows, else `loop`); `tiled128_wins` is the 3x-spread rule
+    against it, `bit_equal` whether both block sizes give the same bits."""
     import torch.nn.functional as F
 
     from dts_amd import ops
@@ -544,16 +549,17 @@ def moe_tiled_probes(ext):
             segs = [(int(o), int(o) + c) for o, c in zip(offsets.tolist(), hist)]
             xs = torch.randn(T * TOP_K, H, dtype=torch.bfloat16, device="cuda")
 
-            def forward(tiled):
+            def forward(tiled, block=64):
                 def fn(_):
-                    moe.tiled = tiled
+                    moe.tiled, moe.tiled_block = tiled, block
                     with torch.inference_mode():
-                        moe(x)
+                        return moe(x)
                 return fn
 
-            def gemms_tiled(_):
-                act = ops.moe_grouped_gemm(xs, moe.gate_up_w, counts, offsets, True)
-                ops.moe_grouped_gemm(act, moe.down_w, counts, offsets)
+            def gemms_tiled(_, block=64):
+                act = ops.moe_grouped_gemm(
+                    xs, moe.gate_up_w, counts, offsets, True, block)
+                return ops.moe_grouped_gemm(act, moe.down_w, counts, offsets, block=block)
 
             def gemms_linear(_):
                 for e, (a, b) in enumerate(segs):
@@ -561,10 +567,13 @@ def moe_tiled_probes(ext):
                              moe.down_w[e])
 
             fns = {"loop": forward(False), "tiled": forward(True),
-                   "gemms_linear": gemms_linear, "gemms_tiled": gemms_tiled}
-            with torch.inference_mode():
-                moe.tiled = True
-                assert moe(x).isfinite().all()
+                   "tiled128": forward(True, 128),
+                   "gemms_linear": gemms_linear, "gemms_tiled": gemms_tiled,
+                   "gemms_tiled128": lambda _: gemms_tiled(_, 128)}
+            out64 = fns["tiled"](0)
+            assert out64.isfinite().all()
+            bit_equal = bool(torch.equal(out64, fns["tiled128"](0))) and bool(
+                torch.equal(gemms_tiled(0), gemms_tiled(0, 128)))
             iters = 20 if T <= 512 else 8
             ts = {k: [] for k in fns}
             for _ in range(5):
@@ -576,7 +585,14 @@ def moe_tiled_probes(ext):
                 rec[f"{k}_us"], rec[f"{k}_spread_us"] = med(ts[k])
             spread = max(rec["loop_spread_us"], rec["tiled_spread_us"])
             rec["tiled_wins"] = rec["loop_us"] - rec["tiled_us"] > 3 * spread
+            rec["parent"] = "tiled" if 66 <= T * TOP_K <= 1024 else "loop"
+            spread = max(rec[rec["parent"] + "_spread_us"], rec["tiled128_spread_us"])
+            rec["tiled128_wins"] = (
+                rec[rec["parent"] + "_us"] - rec["tiled128_us"] > 3 * spread
+            )
+            rec["bit_equal"] = bit_equal
             print(json.dumps(rec), flush=True)
+    moe.tiled_block = 0
 
 
 def moe_route_probes(ext):
